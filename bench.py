@@ -10,7 +10,9 @@ per-GPU batch 8, bf16 storage / fp32 accumulate, synthetic latents (z, hint late
 random-init weights.  One step = p_losses forward + hand-written backward + LoRA-only gradient all-reduce
 (RCCL) + fused AdamW, driven through the drop-in cldm API (ControlFinetuneLDM.p_losses / configure_optimizers).
 
-Prints ONE JSON line (rank 0).  `value` = images/s over all ranks.  Also reported:
+Prints ONE JSON line (rank 0).  `value` = images/s over all ranks, `ms_per_step` = wall time of one timed step.  A plain run
+builds, warms up, times the K steps and prints the line; `--dump-outputs DIR` writes what the last timed step computed
+(dump_outputs).  With --full it also reports:
   roofline      whole-step MFMA roofline: SURVEY.md 8(d) algorithmic FLOPs per image (1.996 TF for r128: forward
                 + data-gradients + LoRA/zero-conv weight-gradients, no recompute, no frozen dW) x images/s / 2.5 PF,
                 plus the dominant kernel (implicit-GEMM conv 320->320 @64x64) timed with HIP events on this stream.
@@ -68,6 +70,19 @@ def provenance(meta, rel="ctrlora_amd/csrc/gemm.hip"):
 
 PEAK_HBM_TBS = 8.0          # TB/s, MI355X_MICROARCH.md
 PEAK_BF16_TFLOPS = 2500.0
+
+
+def configure_optimizers(model):
+    """model.configure_optimizers() from a throw-away working directory: like the reference, it writes its trainable-parameter
+    names to ./tmp/, and the benchmark must neither write into the checkout it runs from nor fail where that is read-only."""
+    import tempfile
+    prev = os.getcwd()
+    with tempfile.TemporaryDirectory(prefix="ctrlora_bench_") as d:
+        os.chdir(d)
+        try:
+            return model.configure_optimizers()
+        finally:
+            os.chdir(prev)
 
 
 def build_model(config, seed, rank_override=None, tiny=False, mutate=None, fast_init=None):
@@ -545,7 +560,7 @@ def pretrain_bench_dp(device, dtype, world, rank, B=8, steps=9, warmup=9, tiny=F
     model.set_engine_dtype(dtype)
     model.learning_rate = 1e-5
     dp = model.init_data_parallel()
-    opt = model.configure_optimizers()
+    opt = configure_optimizers(model)
     tasks = list(model.control_model.tasks)
     data = synth(B, 64, model.control_model.context_dim, device, 4321 + rank, 2)
     rng = np.random.RandomState(97 + rank)          # per-rank task stream, as the reference's unseeded sampler gives
@@ -597,7 +612,7 @@ def pretrain_bench(device, dtype, B=8, steps=9, warmup=9, tiny=False):
     model = build_model("ctrlora_pretrain_sd15_9tasks_rank128.yaml", 0, tiny=tiny).to(device).train()
     model.set_engine_dtype(dtype)
     model.learning_rate = 1e-5
-    opt = model.configure_optimizers()
+    opt = configure_optimizers(model)
     tasks = list(model.control_model.tasks)
     data = synth(B, 64, model.control_model.context_dim, device, 4321, 2)
 
@@ -707,6 +722,25 @@ def cpu_baseline(rank_lora=32, threads=32):
                   sample=f"{S} timed DDIM steps of the oracle with CFG 7.5 (2 forwards each), bs 1, latent 64x64, fp32, "
                          f"{n_thr} threads: {ddim_s:.1f} s per step")
     return train_b, ddim_b
+
+
+DUMP_SAMPLE = 1 << 22     # sampled elements per flat buffer: 2 x 16 MB of float32
+
+
+def dump_outputs(out_dir, loss, executors):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, for output-by-output comparison of two builds --
+    loss.npy (float64 scalar), and params.npy / grads.npy (float32): the trainables' fp32 master copy after the optimizer step and
+    the gradient the step computed (the flat buffers of ctrlora_amd/engine/packing.py, executors concatenated), sampled at
+    DUMP_SAMPLE fixed positions (seed 0, ascending, the same in every run with the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array(float(loss), dtype=np.float64))
+    flat = torch.cat([ex.tr.flat for ex in executors])
+    grad = torch.cat([ex.tr.flat_grad for ex in executors])
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(flat.device)
+    np.save(os.path.join(out_dir, "params.npy"), flat[idx].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grads.npy"), grad[idx].float().cpu().numpy())
 
 
 def _free_port():
@@ -867,6 +901,12 @@ def main():
                     help="launch-path check without the model: the ranks are started, rendezvous on 127.0.0.1, all-reduce a 4 MB "
                          "bucket per step inside the same barrier / MAX-over-ranks bracket as the timed region, rank 0 prints one "
                          "JSON line.  RCCL on GPUs, gloo on a CPU-only host (tests/test_bench_spawn.py runs it with 2 ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the evidence legs around the headline: roofline (dominant-kernel probe, family census), VAE end to "
+                         "end, DDIM, CPU baseline, the stock comparison and (N > 1) the exchange-off re-run.  Without it a run "
+                         "builds, warms up, times the training steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--tag-gemm", default=None, metavar="JSON",
                     help="profiling aid: tag every contraction launch with its product signature (extra empty workgroups, "
                          "csrc/debug_hooks.h) and write the tag table here -- tools/prof_shapes.py joins it with a rocprofv3 "
@@ -934,7 +974,7 @@ def main():
     if world > 1:
         from ctrlora_amd.parallel import GradAllReduce
         model.dp = GradAllReduce([model.control_model.executor()])
-    opt = model.configure_optimizers()
+    opt = configure_optimizers(model)
     B, H = args.batch, 64
     n_in = 4
     data = synth(B, H, model.control_model.context_dim, device, 1234 + rank, n_in)
@@ -998,18 +1038,22 @@ def main():
         dt = float(tmax)
     final_loss = float(loss)
     assert final_loss == final_loss, "loss is NaN"
+    if args.dump_outputs and rank == 0:      # before anything below runs the step again
+        dump_outputs(args.dump_outputs, loss, opt.executors)
 
     dp_info = None
     if world > 1:
-        # what the exchange costs: the same K steps with the gradient all-reduce switched off (every rank then keeps its own
-        # gradients -- measurement only, AFTER the timed region); exposed = with - without
         ex0 = model.control_model.executor()
         dp_info = {"payload_MB_per_step": round(ex0.tr.numel * 4 / 1e6, 1), "collective": "RCCL all-reduce (SUM), fp32, "
                    "LoRA + zero-conv + norm gradients only (flat buffer in backward-completion order)"}
+        if graphed is not None:
+            dp_info.update(segments=len(graphed.segments), bucket_MB=32)
+    if world > 1 and args.full:
+        # what the exchange costs: the same K steps with the gradient all-reduce switched off (every rank then keeps its own
+        # gradients -- measurement only, AFTER the timed region); exposed = with - without
         try:
             if graphed is not None:
                 saved_fn, graphed._reduce_fn = graphed._reduce_fn, (lambda buf: None)
-                dp_info.update(segments=len(graphed.segments), bucket_MB=32)
             else:
                 model.dp.enabled = False
                 opt.pre_step_hook = None
@@ -1049,7 +1093,7 @@ def main():
         }
         if dp_info is not None:
             out["config"]["data_parallel"] = dp_info
-        if world == 1 and args.rank_lora == 128 and args.dtype == "bf16" and not args.tiny and B == 8:
+        if args.full and world == 1 and args.rank_lora == 128 and args.dtype == "bf16" and not args.tiny and B == 8:
             # context, not credit: the reference's own modules on PyTorch-ROCm eager kernels, bf16 autocast, same workload and
             # GPU model (tests/tools/compare_stock.py -> profiles/r02_compare_precision.json); not re-measured in this run
             stock_ips, stock_src = stock_reference()
@@ -1064,39 +1108,40 @@ def main():
                                                   note="the comparator runs PyTorch-ROCm's kernels, not this tree's: stale = no commit recorded"),
                                "kind": f"static: {stock_src} (reference modules, torch.autocast(bf16), PyTorch-ROCm eager, B=8, "
                                        "1x MI355X; tests/tools/compare_stock.py)"}
-        achieved = tf_img * ips / world          # per-GPU TFLOP/s
-        roof = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                "basis": f"{tf_img} TFLOP/image algorithmic (SURVEY.md 8d), per GPU"}
-        roof["whole_step"] = {"achieved": roof["achieved"], "frac": roof["frac"], "basis": roof.pop("basis")}
-        if not args.tiny and args.dtype == "bf16":   # rank 0 only; no collective inside
-            dk = conv_kernel_probe(device, dtype)
-            fam = family_census(model, opt, data)
-            # Contract fields = the DOMINANT KERNEL of the step (gemm_fl_kernel<256 x 160, conv-s1>: 14 % of the step's GPU time,
-            # profiles/r04_prof/train_kernel_stats_steady.txt) at its dominant shape, timed live with HIP events on the launching
-            # stream: the figure the rocprofv3 --stats row of the same launch has to agree with (profiles/r04_prof/
-            # dominant_kernel_stats.csv).  The time-weighted figure of the whole GEMM family, the attention and the HBM-bound
-            # families and the whole step stay alongside -- the whole-step fraction is the honest summary of the step.
-            roof.update(achieved=dk["achieved"], frac=dk["frac"], traffic=dk["traffic"], kernel=dk["kernel"],
-                        ms_per_launch=dk["ms"], algorithmic_bytes_per_launch=43_800_000,
-                        frac_of="the DOMINANT KERNEL at its dominant shape (16 % of the step's GPU time), 30 hot back-to-back "
-                                "launches between HIP events; the step as a whole is roofline.whole_step, the time-weighted "
-                                "contraction family roofline.family -- since round 4 (rounds 1-3 reported the family figure here)",
-                        rocprof=dominant_kernel_rocprof(),
-                        traffic_provenance=dk.get("traffic_provenance"),
-                        traffic_kind="rocprofv3 TCC passes on this launch, FETCH_SIZE (x2: gfx950 correction) + WRITE_SIZE "
-                                     "(profiles/dominant_kernel_traffic.json names the commit and the kernel-source hash it was taken on; "
-                                     "`traffic_provenance.stale` = csrc/gemm.hip has changed since); static in this run")
-            gf = fam.get("gemm")
-            if gf:
-                roof["family"] = dict(gf, kernel="gemm_fl / gemm kernel family (implicit-GEMM 3x3 conv + linear + LoRA-fused linear), "
-                                                 "time-weighted over all shapes of one step")
-            if "attention" in fam:
-                roof["attention_family"] = fam["attention"]
-            if "hbm" in fam:
-                roof["norm_elementwise_family"] = fam["hbm"]
-        out["roofline"] = roof
-    if rank == 0 and not args.tiny and args.dtype == "bf16" and not args.no_vae:
+        if args.full:
+            achieved = tf_img * ips / world          # per-GPU TFLOP/s
+            roof = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": None,
+                    "basis": f"{tf_img} TFLOP/image algorithmic (SURVEY.md 8d), per GPU"}
+            roof["whole_step"] = {"achieved": roof["achieved"], "frac": roof["frac"], "basis": roof.pop("basis")}
+            if not args.tiny and args.dtype == "bf16":   # rank 0 only; no collective inside
+                dk = conv_kernel_probe(device, dtype)
+                fam = family_census(model, opt, data)
+                # Contract fields = the DOMINANT KERNEL of the step (gemm_fl_kernel<256 x 160, conv-s1>: 14 % of the step's GPU time,
+                # profiles/r04_prof/train_kernel_stats_steady.txt) at its dominant shape, timed live with HIP events on the launching
+                # stream: the figure the rocprofv3 --stats row of the same launch has to agree with (profiles/r04_prof/
+                # dominant_kernel_stats.csv).  The time-weighted figure of the whole GEMM family, the attention and the HBM-bound
+                # families and the whole step stay alongside -- the whole-step fraction is the honest summary of the step.
+                roof.update(achieved=dk["achieved"], frac=dk["frac"], traffic=dk["traffic"], kernel=dk["kernel"],
+                            ms_per_launch=dk["ms"], algorithmic_bytes_per_launch=43_800_000,
+                            frac_of="the DOMINANT KERNEL at its dominant shape (16 % of the step's GPU time), 30 hot back-to-back "
+                                    "launches between HIP events; the step as a whole is roofline.whole_step, the time-weighted "
+                                    "contraction family roofline.family -- since round 4 (rounds 1-3 reported the family figure here)",
+                            rocprof=dominant_kernel_rocprof(),
+                            traffic_provenance=dk.get("traffic_provenance"),
+                            traffic_kind="rocprofv3 TCC passes on this launch, FETCH_SIZE (x2: gfx950 correction) + WRITE_SIZE "
+                                         "(profiles/dominant_kernel_traffic.json names the commit and the kernel-source hash it was taken on; "
+                                         "`traffic_provenance.stale` = csrc/gemm.hip has changed since); static in this run")
+                gf = fam.get("gemm")
+                if gf:
+                    roof["family"] = dict(gf, kernel="gemm_fl / gemm kernel family (implicit-GEMM 3x3 conv + linear + LoRA-fused linear), "
+                                                     "time-weighted over all shapes of one step")
+                if "attention" in fam:
+                    roof["attention_family"] = fam["attention"]
+                if "hbm" in fam:
+                    roof["norm_elementwise_family"] = fam["hbm"]
+            out["roofline"] = roof
+    if args.full and rank == 0 and not args.tiny and args.dtype == "bf16" and not args.no_vae:
         try:   # end to end = the core step + the first-stage encodes the reference performs inside every step
             vb = vae_bench(device, dtype, B)
             step_ms = dt / args.steps * 1e3
@@ -1108,7 +1153,7 @@ def main():
             print(f"[bench] VAE leg failed: {type(e).__name__}: {e}", file=sys.stderr)
     # DDIM leg: every rank samples its own batch (replicas, no collective); aggregate = sum over ranks
     ddim = None
-    if not args.no_ddim:
+    if args.full and not args.no_ddim:
         del graphed, model, opt
         torch.cuda.empty_cache()
         try:
@@ -1129,7 +1174,7 @@ def main():
     if rank == 0:
         if ddim is not None:
             out["ddim"] = ddim
-        if world == 1 and not args.no_cpu_baseline and not args.tiny:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.tiny:
             train_b, ddim_b = cpu_baseline()
             out["cpu_baseline"] = train_b
             if ddim is not None:

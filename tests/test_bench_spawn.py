@@ -110,3 +110,58 @@ def test_static_artefacts_the_bench_quotes_carry_commit_and_source_hash(tmp_path
     assert bench.provenance({})["stale"] and bench.provenance(None)["stale"]            # nothing recorded = stale
     ips, src = bench.stock_reference()
     assert ips > 0 and src.startswith("profiles/")
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_last_step(tmp_path):
+    """`--dump-outputs DIR`: loss (float64) and the same DUMP_SAMPLE positions of the fp32 master trainables and their gradient
+    (float32) in every run, whatever the buffer size; well under the 64 MB an output set may take."""
+    import numpy as np
+    import torch
+    n = bench.DUMP_SAMPLE + 12345
+    exs = [types.SimpleNamespace(tr=types.SimpleNamespace(flat=torch.arange(m, dtype=torch.float32) + off,
+                                                          flat_grad=-torch.arange(m, dtype=torch.float32) - off))
+           for m, off in ((n - 1000, 0), (1000, n - 1000))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.25), exs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads.npy", "loss.npy", "params.npy"]
+    loss, p, g = (np.load(tmp_path / "a" / f) for f in ("loss.npy", "params.npy", "grads.npy"))
+    assert loss.dtype == np.float64 and float(loss) == 0.25
+    assert p.dtype == g.dtype == np.float32 and p.shape == g.shape == (bench.DUMP_SAMPLE,)
+    assert np.all(np.diff(p) > 0) and p[-1] < n and np.array_equal(g, -p)      # distinct ascending positions of both executors
+    assert p[-1] >= n - 1000                                                    # the second executor's buffer is sampled too
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    small = [types.SimpleNamespace(tr=types.SimpleNamespace(flat=torch.ones(10), flat_grad=torch.zeros(10)))]
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor(1.0), small)
+    assert np.load(tmp_path / "c" / "params.npy").shape == (10,)
+
+
+def test_optimizer_setup_writes_nothing_into_the_working_directory(tmp_path, monkeypatch):
+    """configure_optimizers() writes its trainable-name report to ./tmp (as the reference does): the benchmark runs it from a
+    throw-away directory, so a read-only checkout works and the checkout stays untouched; the working directory comes back."""
+    monkeypatch.chdir(tmp_path)
+    seen = {}
+
+    class M:
+        def configure_optimizers(self):
+            seen["cwd"] = os.getcwd()
+            os.makedirs("./tmp", exist_ok=True)
+            with open("./tmp/finetune_trainable_params.txt", "w") as f:
+                f.write("x\n")
+            return "opt"
+
+    assert bench.configure_optimizers(M()) == "opt"
+    assert os.getcwd() == str(tmp_path) and os.listdir(tmp_path) == []
+    assert seen["cwd"] != str(tmp_path) and not os.path.exists(seen["cwd"])
+
+    class Boom:
+        def configure_optimizers(self):
+            raise RuntimeError("boom")
+
+    try:
+        bench.configure_optimizers(Boom())
+    except RuntimeError:
+        pass
+    assert os.getcwd() == str(tmp_path)

@@ -13,7 +13,7 @@ else
 fi
 cp gpurun_out/parity_measured.jsonl $O/parity_measured.jsonl 2>/dev/null
 timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log | cut -c1-300
-timeout 900 python bench.py > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log | cut -c1-400
+timeout 900 python bench.py --full > $O/bench.log 2> $O/bench.err; tail -1 $O/bench.log | cut -c1-400
 if [ "$1" != "noprof" ]; then
 rm -rf $O/trace_train
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_train -o train -- python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-ddim --no-vae > $O/trace_train.log 2>&1
