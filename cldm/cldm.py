@@ -194,10 +194,12 @@ class ControlLDM(LatentDiffusion):
             if outer is None:
                 self.__dict__.pop("_hint_cache", None)
 
-    def _run(self, x_noisy, t, cond_txt, hints, weights=None):
+    def _run(self, x_noisy, t, cond_txt, hints, weights=None, context_ip=None):
+        """context_ip: image-prompt tokens for a UNet with IPCrossAttention layers (cldm_ctrlora_style_inference)."""
         eng = self.engine()
         need_grad = torch.is_grad_enabled() and hints is not None and self.training
         if need_grad:
+            assert context_ip is None, "the image-prompt attention is inference only"
             self._sync_trainables()
             from ctrlora_amd.train import ApplyModelFn
             anchor = self._executor_owners()[0].__dict__["_bound"][0]
@@ -206,7 +208,7 @@ class ControlLDM(LatentDiffusion):
         if hints is not None:
             self._sync_trainables()
         return eng.forward(x_noisy, t, cond_txt, hints, control_scales=list(self.control_scales), lora_weights=weights,
-                           only_mid_control=self.only_mid_control)
+                           only_mid_control=self.only_mid_control, context_ip=context_ip)
 
     @torch.no_grad()
     def get_input(self, batch, k, bs=None, *args, **kwargs):

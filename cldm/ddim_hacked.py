@@ -199,7 +199,8 @@ class DDIMSampler(object):
                tuple(float(v) for v in getattr(model, "control_scales", ()) or ()),
                tuple(float(v) for v in (getattr(model, "lora_weights", None) or ())),
                bool(getattr(model, "only_mid_control", False)), bool(self.batch_cfg), bool(self.hoist_hint_encode), _plain(cond),
-               _plain(uncond), WEIGHTS_GENERATION[0])
+               _plain(uncond), WEIGHTS_GENERATION[0],
+               tuple(a.ip_scale for a in model.engine().unet.ip_layers))
         st = self._graph_state if self.reuse_graph else None
         # sample() rebuilds the coefficient table on every call: the kept graph reads ITS table by address (held in st), so a
         # hit needs equal contents, not the same tensor

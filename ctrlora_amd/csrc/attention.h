@@ -25,6 +25,17 @@ struct AttnFwdArgs {
   int q_prescaled;
 };
 
+// Decoupled image-prompt attention (cl_attention_fwd_ip): O gains ip_scale * softmax(scale q K2^T) V2 over Nip <= 64 keys
+// of a second, per-sample context -- a softmax of its own, one masked 64-key tile.  K2 [B*Nip, ldk2]; V2 like V of the
+// same kernel family: bf16 [B*Nip, ldv2] row-major, fp32 [B][inner][ldv2] transposed and zero padded (ldv2 % 64 == 0).
+// A separate kernel argument, so that the plain forwards keep their argument layout.
+struct AttnIpArgs {
+  const void* K2; long ldk2;
+  const void* V2; long ldv2;
+  int Nip;
+  float ip_scale;
+};
+
 struct AttnBwdArgs {
   const void* Q; long ldq; const void* K; long ldk; const void* V; long ldv;
   const void* O; long ldo; const void* dO; long lddo;
@@ -45,6 +56,9 @@ int attn_fwd(const AttnFwdArgs& a, int dtype, hipStream_t st);
 int attn_bwd(const AttnBwdArgs& a, int dtype, hipStream_t st);
 // bf16, no materialised transposes (attention_tr.hip): Vt / Qt / dOt / Kt of the argument blocks are ignored
 int attn_fwd_tr(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st);
+// the same two forwards with the image-prompt tile (AttnFwdArgs::K2 / V2); no LSE
+int attn_fwd_ip(const AttnFwdArgs& a, const AttnIpArgs& ip, int dtype, hipStream_t st);
+int attn_fwd_tr_ip(const AttnFwdArgs& a, const void* V, long ldv, const AttnIpArgs& ip, hipStream_t st);
 int attn_bwd_tr(const AttnBwdArgs& a, hipStream_t st);
 extern int g_attn_fuse_delta;   // 1 = the dQ kernel forms delta (default), 0 = separate attn_delta launch
 extern int g_attn_variant_dkv4;

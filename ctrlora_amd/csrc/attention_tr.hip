@@ -303,6 +303,219 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnFwdArgs p, cons
   }
 }
 
+// =============================================================================== forward + image-prompt tile
+// cl_attention_fwd_ip: the kernel above with TAIL, then one more masked tile of Nip <= 64 image-prompt keys (ip.K2 /
+// ip.V2, prefetched during the last text tile) under a softmax of its own.  The whole image-prompt row is in that one
+// tile, so its max and sum are final before the P.V product: the text part is normalised first (O1 / l1) and P2 is
+// scaled by ip_scale / l2 before it is packed, so the same accumulators end as O1 / l1 + ip_scale * O2 / l2 -- no second
+// set of output registers, Q read once, O written once, no LSE.  (A separate kernel rather than a template flag of the
+// one above: folding the two into one body moved the register allocation of the plain instantiations.)
+template <int DH, int QW>
+__global__ __launch_bounds__(256, 2) void attn_fwd_tr_ip_kernel(AttnFwdArgs p, const void* __restrict__ V, long ldv,
+                                                                AttnIpArgs ip) {
+  using G = Geo<DH>;
+  constexpr int CPR = G::CPR, KSTEPS = G::KSTEPS, DN = G::DN, ROWB = G::ROWB, TILE = G::TILE;
+  constexpr int STAGE = 2 * TILE;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, lq = lane & 15;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int q0 = blockIdx.x * (64 * QW) + wave * (16 * QW);
+  const float sl2 = p.q_prescaled ? 1.0f : p.scale * 1.4426950408889634f;
+
+  u32x4_t qf[QW][KSTEPS];
+#pragma unroll
+  for (int f = 0; f < QW; ++f) {
+    const int row = min(q0 + f * 16 + lq, p.N - 1);
+    const char* qp = (const char*)p.Q + (((long)b * p.N + row) * p.ldq + (long)h * DH) * 2;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+      const int c = 4 * ks + g;
+      qf[f][ks] = (c < CPR) ? *reinterpret_cast<const u32x4_t*>(qp + c * 16) : u32x4_t{0u, 0u, 0u, 0u};
+    }
+  }
+  const char* kbase = (const char*)p.K + ((long)b * p.Nkv * p.ldk + (long)h * DH) * 2;
+  const char* vbase = (const char*)V + ((long)b * p.Nkv * ldv + (long)h * DH) * 2;
+
+  f32x4_t ot[DN][QW];
+#pragma unroll
+  for (int i = 0; i < DN; ++i)
+#pragma unroll
+    for (int f = 0; f < QW; ++f) ot[i][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m_run[QW], l_run[QW];
+#pragma unroll
+  for (int f = 0; f < QW; ++f) { m_run[f] = -1e30f; l_run[f] = 0.f; }
+
+  const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
+  uint32_t krow[KSTEPS];
+#pragma unroll
+  for (int ks = 0; ks < KSTEPS; ++ks) krow[ks] = lq * ROWB + min(4 * ks + g, CPR - 1) * 16;
+  const uint32_t troff = (4 * g + ((lane >> 2) & 3)) * ROWB + (lane & 3) * 8;
+  // S^T = K . Q^T of the K tile at kt (rows = keys 16 kf + 4g + r, col = query lq)
+  auto qk = [&](uint32_t kt, f32x4_t (&st)[4][QW]) {
+    static_for<0, 4>([&](auto KF_) {
+      constexpr int kf = decltype(KF_)::value;
+      u32x4_t ka[KSTEPS];
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) ka[ks] = lds_read_b128_off<kf * 16 * ROWB>(kt + krow[ks]);
+      lds_wait();
+#pragma unroll
+      for (int f = 0; f < QW; ++f) {
+        st[kf][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) Mma<bf16_t>::run(ka[ks], qf[f][ks], st[kf][f]);
+      }
+    });
+  };
+  // O^T += V^T . P^T of the V tile at vt, P = st packed to bf16
+  auto pv = [&](uint32_t vt, f32x4_t (&st)[4][QW]) {
+    u32x4_t pb[2][QW];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int f = 0; f < QW; ++f) {
+        f32x4_t tmp[2] = {st[2 * s][f], st[2 * s + 1][f]};
+        pb[s][f] = PFrag<bf16_t>::make(tmp);
+      }
+    const uint32_t tb = vt + troff;
+    static_for<0, DN>([&](auto I_) {
+      constexpr int i = decltype(I_)::value;
+      u32x4_t va[2];
+      va[0] = tr_frag_off<ROWB, 0, i * 32>(tb);
+      va[1] = tr_frag_off<ROWB, 1, i * 32>(tb);
+      lds_wait();
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int f = 0; f < QW; ++f) Mma<bf16_t>::run(va[s], pb[s][f], ot[i][f]);
+    });
+  };
+
+  const int ntiles = (p.Nkv + 63) / 64;
+  TileDma<DH> dma; dma.init(wave, lane);
+  int koff[TileDma<DH>::NJ], voff[TileDma<DH>::NJ];
+  dma.offsets(p.ldk * 2, koff); dma.offsets(ldv * 2, voff);
+  init_pads<DH>(smem, 4, 0u, 0u, tid, 256);
+  dma.issue(kbase, p.ldk * 2, koff, 0, p.Nkv, smem, wave);
+  dma.issue(vbase, ldv * 2, voff, 0, p.Nkv, smem + TILE, wave);
+  for (int t = 0; t < ntiles; ++t) {
+    const int buf = t & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t + 1 < ntiles) {
+      dma.issue(kbase, p.ldk * 2, koff, (t + 1) * 64, p.Nkv, smem + (buf ^ 1) * STAGE, wave);
+      dma.issue(vbase, ldv * 2, voff, (t + 1) * 64, p.Nkv, smem + (buf ^ 1) * STAGE + TILE, wave);
+    } else {                             // the image-prompt tile: rows past Nip repeat row Nip - 1 (masked below)
+      const char* k2 = (const char*)ip.K2 + ((long)b * ip.Nip * ip.ldk2 + (long)h * DH) * 2;
+      const char* v2 = (const char*)ip.V2 + ((long)b * ip.Nip * ip.ldv2 + (long)h * DH) * 2;
+      dma.offsets(ip.ldk2 * 2, koff); dma.offsets(ip.ldv2 * 2, voff);
+      dma.issue(k2, ip.ldk2 * 2, koff, 0, ip.Nip, smem + (buf ^ 1) * STAGE, wave);
+      dma.issue(v2, ip.ldv2 * 2, voff, 0, ip.Nip, smem + (buf ^ 1) * STAGE + TILE, wave);
+    }
+    const uint32_t kt = lds0 + buf * STAGE, vt = kt + TILE;
+    f32x4_t st[4][QW];
+    qk(kt, st);
+    // ---- online softmax over the text keys (as attn_fwd_tr_kernel<TAIL>)
+    const int kv0 = t * 64;
+#pragma unroll
+    for (int f = 0; f < QW; ++f) {
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (kv0 + kf * 16 + 4 * g + r >= p.Nkv) st[kf][f][r] = -INFINITY;
+          mx = fmaxf(mx, st[kf][f][r]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run[f], mx * sl2);
+      const float alpha = __builtin_amdgcn_exp2f(m_run[f] - m_new);
+      m_run[f] = m_new;
+      float ls = 0.f;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kf][f][r], sl2, -m_new));
+          st[kf][f][r] = e;
+          ls += e;
+        }
+      l_run[f] = l_run[f] * alpha + ls;
+#pragma unroll
+      for (int i = 0; i < DN; ++i) ot[i][f] *= alpha;
+    }
+    pv(vt, st);
+  }
+
+  // ---- text part final: O1 / l1
+#pragma unroll
+  for (int f = 0; f < QW; ++f) {
+    float l = l_run[f];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int i = 0; i < DN; ++i) ot[i][f] *= inv;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  {
+    const uint32_t kt = lds0 + (ntiles & 1) * STAGE, vt = kt + TILE;
+    f32x4_t st[4][QW];
+    qk(kt, st);
+    // ---- the image-prompt softmax, complete within the tile: P2 * ip_scale / l2
+#pragma unroll
+    for (int f = 0; f < QW; ++f) {
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (kf * 16 + 4 * g + r >= ip.Nip) st[kf][f][r] = -INFINITY;
+          mx = fmaxf(mx, st[kf][f][r]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m2 = mx * sl2;                    // key 0 is always real: finite
+      float ls = 0.f;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kf][f][r], sl2, -m2));
+          st[kf][f][r] = e;
+          ls += e;
+        }
+      ls += __shfl_xor(ls, 16, 64);
+      ls += __shfl_xor(ls, 32, 64);
+      const float c = ip.ip_scale / ls;
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf) st[kf][f] *= c;
+    }
+    pv(vt, st);
+  }
+
+  // ---- epilogue: store O rows
+#pragma unroll
+  for (int f = 0; f < QW; ++f) {
+    const int row = q0 + f * 16 + lq;
+    if (row < p.N) {
+      bf16_t* op = reinterpret_cast<bf16_t*>(p.O) + ((long)b * p.N + row) * p.ldo + (long)h * DH;
+#pragma unroll
+      for (int i = 0; i < DN; ++i) {
+        const int d0 = i * 16 + 4 * g;
+        if (d0 < DH) {
+          float v[4] = {ot[i][f][0], ot[i][f][1], ot[i][f][2], ot[i][f][3]};
+          store4(op + d0, v);
+        }
+      }
+    }
+  }
+}
+
 // =============================================================================== forward, ping-pong schedule (description)
 // Self-attention at the 64x64 / 32x32 levels (N = 4096 / 1024 keys, d_head 40 / 80) is where the attention time
 // goes, and there the kernel above is bound by neither pipe: per 32-query x 64-key step a wave issues 28 MFMAs
@@ -1162,6 +1375,42 @@ int attn_fwd_tr(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st) {
     case 40: return launch_fwd_tr_t<40>(a, V, ldv, st);
     case 80: return launch_fwd_tr_t<80>(a, V, ldv, st);
     case 160: return launch_fwd_tr_t<160>(a, V, ldv, st);
+    default: return CL_EINVAL;
+  }
+}
+
+// image-prompt form (cl_attention_fwd_ip): the same grid choice as launch_fwd_tr
+template <int DH>
+static int launch_fwd_tr_ip(const AttnFwdArgs& a, const void* V, long ldv, const AttnIpArgs& ip, hipStream_t st) {
+  constexpr int LDS = 2 * 2 * Geo<DH>::TILE + 64 + 16 * Geo<DH>::ROWB;
+  constexpr int QW = DH <= 80 ? 2 : 1;
+  static bool done = false;
+  if (!done) {
+    if (set_lds(&attn_fwd_tr_ip_kernel<DH, QW>, LDS) || set_lds(&attn_fwd_tr_ip_kernel<DH, 1>, LDS)) return CL_ELAUNCH;
+    done = true;
+  }
+  const long blocks128 = (long)((a.N + 127) / 128) * a.H * a.B;
+  if (QW == 2 && blocks128 >= 512) {
+    dim3 grid((a.N + 127) / 128, a.H, a.B);
+    hipLaunchKernelGGL((attn_fwd_tr_ip_kernel<DH, QW>), grid, dim3(256), LDS, st, a, V, ldv, ip);
+  } else {
+    dim3 grid((a.N + 63) / 64, a.H, a.B);
+    hipLaunchKernelGGL((attn_fwd_tr_ip_kernel<DH, 1>), grid, dim3(256), LDS, st, a, V, ldv, ip);
+  }
+  CL_CHECK_LAUNCH();
+  return CL_OK;
+}
+
+int attn_fwd_tr_ip(const AttnFwdArgs& a, const void* V, long ldv, const AttnIpArgs& ip, hipStream_t st) {
+  if ((a.ldq * 2) % 16 || (a.ldk * 2) % 16 || (ldv * 2) % 16 || (a.ldo * 2) % 16 || a.Nkv < 1 || a.N < 1) return CL_EINVAL;
+  if ((ip.ldk2 * 2) % 16 || (ip.ldv2 * 2) % 16 || ip.Nip < 1 || ip.Nip > 64 || !ip.K2 || !ip.V2 || a.LSE) return CL_EINVAL;
+  switch (a.DH) {
+    case 8: return launch_fwd_tr_ip<8>(a, V, ldv, ip, st);
+    case 16: return launch_fwd_tr_ip<16>(a, V, ldv, ip, st);
+    case 32: return launch_fwd_tr_ip<32>(a, V, ldv, ip, st);
+    case 40: return launch_fwd_tr_ip<40>(a, V, ldv, ip, st);
+    case 80: return launch_fwd_tr_ip<80>(a, V, ldv, ip, st);
+    case 160: return launch_fwd_tr_ip<160>(a, V, ldv, ip, st);
     default: return CL_EINVAL;
   }
 }

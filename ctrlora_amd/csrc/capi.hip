@@ -249,6 +249,20 @@ int cl_attention_fwd_v2(int dtype, const void* Q, long ldq, const void* K, long 
   return attn_fwd_tr(a, V, ldv, S(stream));
 }
 
+int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
+                        const void* Kip, long ldkip, const void* Vip, long ldvip, void* O, long ldo, int B, int H, int N,
+                        int Nkv, int Nip, int dh, float scale, float ip_scale, int flags, void* stream) {
+  if (flags & ~CL_ATTN_Q_PRESCALED) return CL_EINVAL;
+  AttnFwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.O = O; a.ldo = ldo;
+  a.B = B; a.H = H; a.N = N; a.Nkv = Nkv; a.DH = dh; a.scale = scale;
+  a.q_prescaled = (flags & CL_ATTN_Q_PRESCALED) ? 1 : 0;
+  AttnIpArgs ip{}; ip.K2 = Kip; ip.ldk2 = ldkip; ip.V2 = Vip; ip.ldv2 = ldvip; ip.Nip = Nip; ip.ip_scale = ip_scale;
+  if (dtype == CL_BF16) return attn_fwd_tr_ip(a, V, ldv, ip, S(stream));
+  if (ldv < 1 || ldv > 0x7fffffffL) return CL_EINVAL;
+  a.Vt = V; a.nkv_pad = (int)ldv;
+  return attn_fwd_ip(a, ip, dtype, S(stream));
+}
+
 int cl_attention_bwd_v2(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                         const void* O, long ldo, const void* dO, long lddo, const float* LSE, float* Delta,
                         int lse_stride, void* dQ, long lddq, void* dK, long lddk, void* dV, long lddv, int B, int H,

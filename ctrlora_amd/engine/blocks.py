@@ -456,6 +456,19 @@ class AttnE:
         # log2-domain scores straight off the matrix product; dQ / dK / dV stay the gradients of the TRUE q, k, v, so the
         # projections' backward is unchanged.  q is internal to the block (attention.py:163-171: only the attention reads it).
         self.q_alpha = self.scale * 1.4426950408889634
+        # IP-Adapter image prompt (ldm/modules/attention_ip.py IPCrossAttention; frozen UNet only): [to_k_ip | to_v_ip]
+        # packed like fused_kv, and the layer's ip_scale.  At scale 0 (or without an image-prompt context) fwd is the
+        # plain cross-attention: the reference's out + 0 * out_ip equals out for finite values.
+        self.kv_ip: Optional[LinearW] = None
+        self.ip_scale = 0.0
+
+    def ip_live(self) -> bool:
+        return self.kv_ip is not None and self.ip_scale != 0.0
+
+    def project_ip(self, ctx: Ctx, c_ip):
+        """K / V projections of the image-prompt tokens [B*Nip, context_dim] (identical for every denoising step)."""
+        kv, _ = linear_fwd(ctx, self.kv_ip, c_ip)
+        return kv[:, :self.inner], kv[:, self.inner:]
 
     def _prescaled(self, ctx: Ctx) -> bool:
         return PRESCALE_Q and ctx.dtype == torch.bfloat16
@@ -507,9 +520,12 @@ class AttnE:
         v, tv = linear_fwd(ctx, self.v, c)
         return k, v, tk, tv
 
-    def fwd(self, ctx: Ctx, xn, c, B, N, Nkv, residual, kv_cache=None, ln=None):
+    def fwd(self, ctx: Ctx, xn, c, B, N, Nkv, residual, kv_cache=None, ln=None, ip=None):
         """ln = LayerNormOp.prologue(...): xn is the UN-normalised input and the product that reads it applies the norm
-        (only where ln_fusable() said so)."""
+        (only where ln_fusable() said so).  ip = (k_ip, v_ip, Nip): image-prompt K / V of an IPCrossAttention, used when
+        ip_live(); softmax over the text keys + ip_scale * softmax over the image-prompt keys in one launch."""
+        if ip is not None and self.ip_live():
+            return self._fwd_ip(ctx, xn, c, B, N, Nkv, residual, kv_cache, ln, ip)
         inner, H = self.inner, self.heads
         tq = tk = tv = None
         pre = self._prescaled(ctx)
@@ -548,6 +564,27 @@ class AttnE:
         out, to_ = linear_fwd(ctx, self.o, a, residual=residual)
         saved = (xn, c, q, k, v, a, lse, tq, tk, tv, to_) if ctx.record else None
         return out, saved
+
+    def _fwd_ip(self, ctx: Ctx, xn, c, B, N, Nkv, residual, kv_cache, ln, ip):
+        assert not self.is_self and not ctx.record, "the image-prompt attention is inference only"
+        inner, H = self.inner, self.heads
+        pre = self._prescaled(ctx)
+        q, _ = linear_fwd(ctx, self.q, xn, alpha=self.q_alpha if pre else 1.0, ln=ln)
+        k, v = (kv_cache if kv_cache is not None else self.project_context(ctx, c))[:2]
+        k_ip, v_ip, Nip = ip
+        a = ctx.new(B * N, inner)
+        if ctx.dtype == torch.bfloat16:
+            hip.attention_fwd_ip(q, k, v, k_ip, v_ip, a, B, H, N, Nkv, Nip, self.dh, self.scale, self.ip_scale,
+                                 q_prescaled=pre)
+        else:
+            vt = torch.empty((B, inner, rup(Nkv, 64)), dtype=ctx.dtype, device=ctx.device)
+            hip.transpose(v, vt, B, Nkv, inner, vt.shape[-1], ldi=v.stride(0))
+            vt_ip = torch.empty((B, inner, 64), dtype=ctx.dtype, device=ctx.device)
+            hip.transpose(v_ip, vt_ip, B, Nip, inner, 64, ldi=v_ip.stride(0))
+            hip.attention_fwd_ip(q, k, vt, k_ip, vt_ip, a, B, H, N, Nkv, Nip, self.dh, self.scale, self.ip_scale)
+            del vt, vt_ip
+        out, _ = linear_fwd(ctx, self.o, a, residual=residual)
+        return out, None
 
     def bwd(self, ctx: Ctx, dout, saved, B, N, Nkv, accum_xn=None):
         """dout: gradient of the block output (residual path handled by the caller).
@@ -640,7 +677,7 @@ class SpatialTransformerE:
         self.ff_proj, self.ff_out = ff_proj, ff_out
         self.C = proj_in.N
 
-    def fwd(self, ctx: Ctx, x, c, B, H, W, Nkv, out=None, kv_cache=None):
+    def fwd(self, ctx: Ctx, x, c, B, H, W, Nkv, out=None, kv_cache=None, ip=None):
         N = H * W
         xn, st0 = self.norm.fwd(ctx, x, B, N)
         h0, _ = linear_fwd(ctx, self.proj_in, xn)                    # 1x1 conv == per-token linear
@@ -663,7 +700,7 @@ class SpatialTransformerE:
         else:
             l2 = None
             n2, s2 = self.ln2.fwd(ctx, h1)
-        h2, sv2 = self.attn2.fwd(ctx, n2, c, B, N, Nkv, residual=h1, kv_cache=kv_cache, ln=l2)
+        h2, sv2 = self.attn2.fwd(ctx, n2, c, B, N, Nkv, residual=h1, kv_cache=kv_cache, ln=l2, ip=ip)
         L = self.ff_proj
         ff_live = (bool(L.r) and not (L.Wm is not None and not ctx.record)) or (ctx.record and L.tW is not None)
         xs_geglu = (not ctx.record and ctx.dtype == torch.bfloat16 and L.N % 64 == 0

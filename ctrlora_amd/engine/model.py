@@ -49,14 +49,17 @@ class CtrLoRAEngine:
         return self
 
     @torch.no_grad()
-    def forward_external_control(self, x_noisy, t, context, control: Optional[list], only_mid_control=False):
+    def forward_external_control(self, x_noisy, t, context, control: Optional[list], only_mid_control=False,
+                                 context_ip=None):
         """ControlledUnetModel.forward with caller-supplied NCHW residuals (cldm/cldm.py:22-45); like the
-        reference it consumes `control` with pop()."""
+        reference it consumes `control` with pop().  context_ip (B, Nip, D): image-prompt tokens of the UNet's
+        IPCrossAttention layers (cldm/cldm_style.py), or None."""
         B, _, H, W = x_noisy.shape
         ctx = Ctx(self.dtype, self.device, False)
         t = t.to(device=self.device, dtype=torch.long).contiguous()
         c = self._ctx_in(context)
-        semb, hs, dims, h_mid = self.unet.encode(ctx, self._tok_in(x_noisy), t, c, B, H, W)
+        cip = self._ip_in(context_ip, B)
+        semb, hs, dims, h_mid = self.unet.encode(ctx, self._tok_in(x_noisy), t, c, B, H, W, c_ip=cip)
         bufs = self.unet.alloc_decoder_inputs(ctx, B, dims)
         self.unet.fill_without_control(ctx, bufs, hs, h_mid)
         if control is not None:
@@ -68,7 +71,7 @@ class CtrLoRAEngine:
                     break
                 ck = control.pop()
                 hip.axpby(self._tok_in(ck)[:, :sinks[k][0].shape[1]], sinks[k][0], 1.0, 1.0)
-        eps_tok, _ = self.unet.decode(ctx, bufs, semb, c, B, dims[-1])
+        eps_tok, _ = self.unet.decode(ctx, bufs, semb, c, B, dims[-1], c_ip=cip)
         eps = torch.empty((B, self.cfg.out_channels, H, W), dtype=torch.float32, device=self.device)
         return hip.tok_to_nchw(eps_tok, eps)
 
@@ -83,6 +86,13 @@ class CtrLoRAEngine:
         out = torch.empty((B * L, D), dtype=self.dtype, device=self.device)
         return hip.pack2d(c.float().reshape(B * L, D), out)
 
+    def _ip_in(self, c_ip: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        """Image-prompt tokens (B, Nip, D) -> [B*Nip, D] in the engine dtype; None when no UNet layer would read them."""
+        if c_ip is None or not self.unet.ip_layers:
+            return None
+        assert c_ip.dim() == 3 and c_ip.shape[0] == B and 1 <= c_ip.shape[1] <= 64, tuple(c_ip.shape)
+        return self._ctx_in(c_ip)
+
     def reset_context_cache(self):
         self._kv = None
 
@@ -94,13 +104,16 @@ class CtrLoRAEngine:
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, x_noisy, t, context, hints: Optional[Sequence[torch.Tensor]], control_scales=None,
-                lora_weights=None, record: bool = False, only_mid_control: bool = False) -> torch.Tensor:
+                lora_weights=None, record: bool = False, only_mid_control: bool = False, context_ip=None) -> torch.Tensor:
         """x_noisy (B,4,H,W) fp32, t (B,) int64, context (B,L,D), hints: one latent (B,4,H,W) per
-        ControlNet bank or None (plain UNet).  Returns eps (B,out_channels,H,W) fp32."""
+        ControlNet bank or None (plain UNet).  context_ip (B,Nip,D): image-prompt tokens for the UNet's
+        IPCrossAttention layers (inference only; the ControlNets never see them).  Returns eps (B,out_channels,H,W) fp32."""
         B, _, H, W = x_noisy.shape
         ctx = Ctx(self.dtype, self.device, record)
         t = t.to(device=self.device, dtype=torch.long).contiguous()
         c = self._ctx_in(context)
+        cip = self._ip_in(context_ip, B)
+        assert cip is None or not record, "the image-prompt attention is inference only"
         kvs = None
         if self.cache_context_kv and not record:
             if self._kv is None:
@@ -123,7 +136,7 @@ class CtrLoRAEngine:
                 for i, (cn, ht) in enumerate(zip(self.controls, hint_toks)):
                     trunks.append(cn.fwd_trunk(ctx_cn, ht, t, c, B, H, W, kv=None if kvs is None else kvs["cn"][i]))
         semb, hs, dims, h_mid = self.unet.encode(ctx, self._tok_in(x_noisy), t, c, B, H, W,
-                                                 kv=None if kvs is None else kvs["unet"])
+                                                 kv=None if kvs is None else kvs["unet"], c_ip=cip)
         if overlap:
             torch.cuda.current_stream().wait_stream(self._side)
         bufs = self.unet.alloc_decoder_inputs(ctx, B, dims)
@@ -155,7 +168,8 @@ class CtrLoRAEngine:
                              kv=None if kvs is None else kvs["cn"][i])
                 cn_recs.append((rec, weights[i]))
         del hs
-        eps_tok, dec_rec = self.unet.decode(ctx, bufs, semb, c, B, dims[-1], kv=None if kvs is None else kvs["unet"])
+        eps_tok, dec_rec = self.unet.decode(ctx, bufs, semb, c, B, dims[-1], kv=None if kvs is None else kvs["unet"],
+                                            c_ip=cip)
         eps = torch.empty((B, self.cfg.out_channels, H, W), dtype=torch.float32, device=self.device)
         hip.tok_to_nchw(eps_tok, eps)
         if record:

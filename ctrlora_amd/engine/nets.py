@@ -190,6 +190,15 @@ class _Builder:
             self.groups += [g1, g2]
         attn1 = AttnE(a1[0], a1[1], a1[2], a1[3], heads, True, fused_qkv=fq, group=g1)
         attn2 = AttnE(a2[0], a2[1], a2[2], a2[3], heads, False, fused_kv=fkv, need_kv_grad=lora, group=g2)
+        if not lora and self._has(f"{tb}.attn2.to_k_ip.weight"):
+            # IPCrossAttention (ldm/modules/attention_ip.py): frozen to_k_ip | to_v_ip and the per-layer ip_scale buffer
+            attn2.kv_ip = self.fused([f"{tb}.attn2.to_k_ip", f"{tb}.attn2.to_v_ip"])
+            sn = f"{tb}.attn2.ip_scale"
+
+            def load_scale():
+                attn2.ip_scale = float(self._g(sn)) if self._has(sn) else 0.0
+            load_scale()
+            self.frozen.append(load_scale)
         return SpatialTransformerE(norm, proj_in, ln1, attn1, ln2, attn2, ln3, ff_proj, ff_out, proj_out)
 
 
@@ -197,7 +206,8 @@ class _Builder:
 
 class _Env:
     """Mutable per-pass state threaded through the layers."""
-    __slots__ = ("B", "H", "W", "semb", "c", "Nkv", "dsemb", "emb_grads", "kv", "emb_all", "kv_all", "emb_pre", "de_all")
+    __slots__ = ("B", "H", "W", "semb", "c", "Nkv", "dsemb", "emb_grads", "kv", "emb_all", "kv_all", "emb_pre", "de_all",
+                 "c_ip")
 
     def __init__(self, B, H, W, semb, c, Nkv):
         self.B, self.H, self.W, self.semb, self.c, self.Nkv = B, H, W, semb, c, Nkv
@@ -208,6 +218,7 @@ class _Env:
         self.kv_all = None       # frozen UNet: every cross-attention's K / V of the context, one product
         self.emb_pre = None      # ControlNet: {id(_Res): (emb_layers output, x A^T)} formed by grouped launches up front
         self.de_all = None       # ControlNet backward: fp32 [B, sum cout] -- every grouped ResBlock's d emb_out lands in its slice
+        self.c_ip = None         # frozen UNet with IP-Adapter layers: image-prompt tokens [B*Nip, context_dim]
 
 
 class _Res:
@@ -250,7 +261,17 @@ class _ST:
             inner = self.blk.attn2.inner
             cache = (env.kv_all[:, self.kv_off:self.kv_off + inner],
                      env.kv_all[:, self.kv_off + inner:self.kv_off + 2 * inner], None, None)
-        return self.blk.fwd(ctx, x, env.c, env.B, env.H, env.W, env.Nkv, out=out, kv_cache=cache)
+        ip = None
+        a2 = self.blk.attn2
+        if env.c_ip is not None and a2.ip_live():
+            # the image-prompt K / V: made once per sampling run like the text context's (per-key cache)
+            kv = None if env.kv is None else env.kv.get(self.key + "/ip")
+            if kv is None:
+                kv = a2.project_ip(ctx, env.c_ip)
+                if env.kv is not None:
+                    env.kv[self.key + "/ip"] = kv
+            ip = (kv[0], kv[1], env.c_ip.shape[0] // env.B)
+        return self.blk.fwd(ctx, x, env.c, env.B, env.H, env.W, env.Nkv, out=out, kv_cache=cache, ip=ip)
 
     def bwd(self, ctx, dy, saved, env, out=None):
         return self.blk.bwd(ctx, dy, saved, env.B, env.H, env.W, env.Nkv, out=out)
@@ -715,6 +736,7 @@ class UNetE:
                 bias = None if fk[0].bias is None else torch.cat([f.bias for f in fk], 0)
                 self.kv_all_w = LinearW(torch.cat([f.W.float() for f in fk], 0), bias, dtype, device, need_bwd=False)
         self._pre = None         # (semb, emb_all output, c, kv_all output) of the running pass: encode -> decode
+        self.ip_layers = [l.blk.attn2 for l in layers if isinstance(l, _ST) and l.blk.attn2.kv_ip is not None]
 
     def _precompute(self, ctx: Ctx, env: _Env, with_kv: bool):
         if self.emb_all is not None:
@@ -724,12 +746,12 @@ class UNetE:
         self._pre = (env.semb, env.emb_all, env.c, env.kv_all)
 
     # -- encoder + middle (never needs gradients: cldm/cldm.py:25-32 runs it under no_grad)
-    def encode(self, ctx: Ctx, x_tok, t, c, B, H, W, kv=None):
+    def encode(self, ctx: Ctx, x_tok, t, c, B, H, W, kv=None, c_ip=None):
         rec = ctx.record
         ctx.record = False
         semb, _ = self.time.fwd(ctx, t)
         env = _Env(B, H, W, semb, c, c.shape[0] // B)
-        env.kv = kv
+        env.kv, env.c_ip = kv, c_ip
         self._precompute(ctx, env, with_kv=kv is None)
         hs, dims = [], []
         h = x_tok
@@ -766,9 +788,10 @@ class UNetE:
             hip.axpby(hs[k], bufs[i][:, self.dec_c1[i]:], 1.0, 0.0)
         hip.axpby(h_mid, bufs[0][:, :self.dec_c1[0]], 1.0, 0.0)
 
-    def decode(self, ctx: Ctx, bufs, semb, c, B, dims_mid, kv=None):
+    def decode(self, ctx: Ctx, bufs, semb, c, B, dims_mid, kv=None, c_ip=None):
         env = _Env(B, dims_mid[0], dims_mid[1], semb, c, c.shape[0] // B)
-        env.kv = kv
+        env.kv, env.c_ip = kv, c_ip
+        assert c_ip is None or not ctx.record, "the image-prompt attention is inference only"
         pre = self._pre
         if pre is not None and pre[0] is semb and pre[2] is c:      # the batched products of THIS pass (encode made them)
             env.emb_all, env.kv_all = pre[1], pre[3]

@@ -85,6 +85,7 @@ _SIGS = {
     "cl_attention_bwd": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _I, _P, _I, _P, _P, _I, _P, _L, _P, _L,
                          _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "cl_attention_fwd_v2": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P],
+    "cl_attention_fwd_ip": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P],
     "cl_attention_bwd_v2": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _I, _P, _L, _P, _L, _P, _L,
                             _I, _I, _I, _I, _I, _F, _I, _P, _P],
     "cl_geglu_fwd": [_I, _P, _L, _P, _L, _L, _I, _P],
@@ -456,6 +457,20 @@ def attention_fwd_v2(q, k, v, o, lse, B, H, N, Nkv, dh, scale, q_prescaled=False
     _chk(lib().cl_attention_fwd_v2(dt(q), q.data_ptr(), ld(q), k.data_ptr(), ld(k), v.data_ptr(), ld(v), o.data_ptr(),
                                    ld(o), ptr(lse), 0 if lse is None else lse.shape[-1], B, H, N, Nkv, dh, scale,
                                    ATTN_Q_PRESCALED if q_prescaled else 0, stream()), "cl_attention_fwd_v2")
+    return o
+
+
+def attention_fwd_ip(q, k, v, k_ip, v_ip, o, B, H, N, Nkv, Nip, dh, scale, ip_scale, q_prescaled=False):
+    """o = softmax(scale q k^T) v + ip_scale * softmax(scale q k_ip^T) v_ip per head, one launch (cl_attention_fwd_ip).
+    k_ip [B*Nip, >=H*dh] (one image prompt per sample, Nip <= 64).  bf16: v / v_ip row-major like k; fp32: v / v_ip
+    transposed [B, H*dh, pad64] (as attention_fwd)."""
+    if dt(q) == BF16:
+        lv, lvi = ld(v), ld(v_ip)
+    else:
+        lv, lvi = v.shape[-1], v_ip.shape[-1]
+    _chk(lib().cl_attention_fwd_ip(dt(q), q.data_ptr(), ld(q), k.data_ptr(), ld(k), v.data_ptr(), lv, k_ip.data_ptr(),
+                                   ld(k_ip), v_ip.data_ptr(), lvi, o.data_ptr(), ld(o), B, H, N, Nkv, Nip, dh, scale,
+                                   ip_scale, ATTN_Q_PRESCALED if q_prescaled else 0, stream()), "cl_attention_fwd_ip")
     return o
 
 

@@ -247,6 +247,15 @@ int cl_attention_bwd_v2(int dtype, const void* Q, long ldq, const void* K, long 
                         const void* O, long ldo, const void* dO, long lddo, const float* LSE, float* Delta,
                         int lse_stride, void* dQ, long lddq, void* dK, long lddk, void* dV, long lddv,
                         int B, int H, int N, int Nkv, int dh, float scale, int flags, void* row_ws, void* stream);
+/* Decoupled image-prompt cross-attention forward (IP-Adapter, ldm/modules/attention_ip.py IPCrossAttention):
+ *   O = softmax(scale q K^T) V + ip_scale * softmax(scale q Kip^T) Vip
+ * two separate softmaxes, fp32 scores, one launch (Q read once, O written once).  Kip / Vip hold Nip (1..64) keys per
+ * batch sample, Kip [B*Nip, ldkip].  V / Vip follow the plain forward of the dtype: bf16 as cl_attention_fwd_v2 (row-major,
+ * ldv / ldvip are row pitches; CL_ATTN_Q_PRESCALED allowed), fp32 as cl_attention_fwd (transposed [B][H*dh][pad] and zero
+ * padded: ldv / ldvip are the key pitches, multiples of 64).  Forward only, no LSE.  Added in ABI 7 (compatible). */
+int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
+                        const void* Kip, long ldkip, const void* Vip, long ldvip, void* O, long ldo, int B, int H,
+                        int N, int Nkv, int Nip, int dh, float scale, float ip_scale, int flags, void* stream);
 /* row_ws (ABI 6; may be NULL): scratch of B * H * lse_stride * 32 bytes, 16-byte aligned.  With CL_ATTN_Q_PRESCALED and
  * d_head 40 the backward kernels keep (-lse, -delta) of every query row there as bf16 triples and feed them through spare
  * contraction slots of the matrix products, which then deliver s - lse and dP - delta (attention.py:171-192's backward with

@@ -104,7 +104,7 @@ def _check_supported(num_res_blocks, channel_mult, num_heads, num_head_channels,
 
 
 def build_encoder(net, in_channels, model_channels, num_res_blocks, attention_resolutions, dropout, channel_mult,
-                  conv_resample, dims, use_checkpoint, num_heads, context_dim, on_block=None):
+                  conv_resample, dims, use_checkpoint, num_heads, context_dim, on_block=None, st_cls=SpatialTransformer):
     """time_embed + input_blocks + middle_block, shared by UNetModel and ControlNet
     (openaimodel.py:526-657, cldm/cldm.py:131-277).  `on_block(ch)` is called after every input block."""
     ted = model_channels * 4
@@ -119,8 +119,8 @@ def build_encoder(net, in_channels, model_channels, num_res_blocks, attention_re
                                use_checkpoint=use_checkpoint)]
             ch = mult * model_channels
             if ds in attention_resolutions:
-                layers.append(SpatialTransformer(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim,
-                                                 use_checkpoint=use_checkpoint))
+                layers.append(st_cls(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim,
+                                     use_checkpoint=use_checkpoint))
             net.input_blocks.append(TimestepEmbedSequential(*layers))
             chans.append(ch)
             if on_block:
@@ -133,13 +133,14 @@ def build_encoder(net, in_channels, model_channels, num_res_blocks, attention_re
             ds *= 2
     net.middle_block = TimestepEmbedSequential(
         ResBlock(ch, ted, dropout, dims=dims, use_checkpoint=use_checkpoint),
-        SpatialTransformer(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim,
-                           use_checkpoint=use_checkpoint),
+        st_cls(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim, use_checkpoint=use_checkpoint),
         ResBlock(ch, ted, dropout, dims=dims, use_checkpoint=use_checkpoint))
     return chans, ch, ds
 
 
 class UNetModel(nn.Module, EngineHost):
+    st_cls = SpatialTransformer      # openaimodel_ip.UNetModel: the IP-Adapter transformer (ldm/modules/attention_ip.py)
+
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None,
                  use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1, num_heads_upsample=-1,
@@ -163,7 +164,7 @@ class UNetModel(nn.Module, EngineHost):
         self.dtype = torch.float16 if use_fp16 else torch.float32
         chans, ch, ds = build_encoder(self, in_channels, model_channels, self.num_res_blocks, self.attention_resolutions,
                                       dropout, self.channel_mult, conv_resample, dims, use_checkpoint, num_heads,
-                                      context_dim)
+                                      context_dim, st_cls=self.st_cls)
         ted = model_channels * 4
         self.output_blocks = nn.ModuleList([])
         for level, mult in list(enumerate(self.channel_mult))[::-1]:
@@ -173,8 +174,8 @@ class UNetModel(nn.Module, EngineHost):
                                    use_checkpoint=use_checkpoint)]
                 ch = model_channels * mult
                 if ds in self.attention_resolutions:
-                    layers.append(SpatialTransformer(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim,
-                                                     use_checkpoint=use_checkpoint))
+                    layers.append(self.st_cls(ch, num_heads, ch // num_heads, depth=1, context_dim=context_dim,
+                                              use_checkpoint=use_checkpoint))
                 if level and i == self.num_res_blocks[level]:
                     layers.append(Upsample(ch, conv_resample, dims=dims, out_channels=ch))
                     ds //= 2
