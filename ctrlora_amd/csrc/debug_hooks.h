@@ -33,6 +33,8 @@ int cl_debug_gemm_xs_rules(int on);
 /* LDS ring depth of the weight-gradient kernel: 3 (default since round 5: three workgroups per CU), 4 or 6 */
 int cl_debug_wgrad_ring(int slots);
 int cl_debug_gemm_tag_count(void);
+/* empties the launch-tag table (it holds 255 signatures: a process that tags several models in turn clears it between them) */
+int cl_debug_gemm_tag_clear(void);
 int cl_debug_gemm_tag_get(int i, long* out12);
 #ifdef __cplusplus
 }

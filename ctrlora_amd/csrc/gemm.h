@@ -121,6 +121,7 @@ extern int g_gemm_tag_on;
 int gemm_cur_tag();                                   // tag of the product being launched on this thread (0 = tagging off)
 void gemm_tag_note(long real_wgs, int wg_size);       // the main kernel's real grid, for the table
 int gemm_tag_count();
+void gemm_tag_clear();
 int gemm_tag_get(int i, long* out12);
 
 }  // namespace cl

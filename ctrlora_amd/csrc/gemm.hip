@@ -76,6 +76,7 @@ void gemm_tag_note(long real_wgs, int wg_size) {
   if (t_tag > 0 && t_tag <= (int)g_tags.size()) { g_tags[t_tag - 1].v[9] = real_wgs; g_tags[t_tag - 1].v[10] = wg_size; }
 }
 int gemm_tag_count() { return (int)g_tags.size(); }
+void gemm_tag_clear() { g_tags.clear(); t_tag = 0; }
 int gemm_tag_get(int i, long* out) {
   if (i < 0 || i >= (int)g_tags.size()) return CL_EINVAL;
   for (int k = 0; k < 12; ++k) out[k] = g_tags[i].v[k];

@@ -126,6 +126,7 @@ _DEBUG_SIGS = {
     "cl_debug_gemm_xs_rules": [_I],
     "cl_debug_wgrad_ring": [_I],
     "cl_debug_gemm_tag_count": [],
+    "cl_debug_gemm_tag_clear": [],
     "cl_debug_gemm_tag_get": [_I, _P],
 }
 

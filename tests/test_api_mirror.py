@@ -165,3 +165,39 @@ def test_switchable_holders_run_standalone_and_inference_net_tracks_the_active_b
     lin = net.get_submodule(net._linear_names[0])
     assert lin.lora_layer is net.loras_list[1][0]
     assert "forward" in ControlNetInference.__dict__      # the module itself is callable after switch_lora (GPU test: test_gpu_parity.py)
+
+
+@pytest.mark.parametrize("name", [f"{pre}{r}{post}" for r in (64, 256, 512)
+                                  for pre, post in (("ctrlora_finetune_sd15_rank", ".yaml"), ("inference/ctrlora_sd15_rank", "_1lora.yaml"))])
+def test_shipped_rank_yamls_build_with_their_rank_in_every_lora_tensor(name):
+    """The six YAMLs of ranks 64 / 256 / 512 build through the class API (bench.build_model: instantiate_from_config on the
+    whole model, encoders replaced by Identity; narrow width, the YAML's own lora_rank) and every LoRA tensor of the state
+    dict is (R, cin) / (cout, R) of the linear it sits on (cldm/lora.py:237-254), R read from the file name."""
+    import re
+    import bench
+    R = int(re.search(r"rank(\d+)", name).group(1))
+
+    def narrow(p):
+        for k in ("control_stage_config", "unet_config"):
+            p[k]["params"].update(model_channels=64, context_dim=96)
+
+    model = bench.build_model(name, 0, mutate=narrow, fast_init=False)
+    cn = model.control_model
+    assert _cfg(name)["model"]["params"]["control_stage_config"]["params"]["lora_rank"] == R
+    if hasattr(cn, "switch_lora"):
+        cn.switch_lora(0)                     # the inference tree keeps its banks apart until one is switched in
+    sd = cn.state_dict()
+    downs = [k for k in sd if k.endswith("lora_layer.down.weight")]
+    ref = json.load(open(os.path.join(GOLDEN, "keys_sd15.json")))["controlnet"]        # the reference's own key list (rank 128)
+    assert sorted(downs) == sorted(k for k in ref if k.endswith("lora_layer.down.weight")) and len(downs) == 82
+    for k in downs:
+        base = sd[k[:-len("lora_layer.down.weight")] + "weight"]
+        up = sd[k[:-len("down.weight")] + "up.weight"]
+        cout, cin = base.shape
+        assert tuple(sd[k].shape) == (R, cin) and tuple(up.shape) == (cout, R), (k, sd[k].shape, up.shape)
+    # no LoRA tensor of another rank hides elsewhere in the tree (bank lists included)
+    for k, v in sd.items():
+        if ".down.weight" in k:
+            assert v.shape[0] == R, (k, v.shape)
+        elif ".up.weight" in k:
+            assert v.shape[1] == R, (k, v.shape)

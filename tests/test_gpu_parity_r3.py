@@ -429,18 +429,22 @@ def test_pretraining_bf16_error_is_flat_on_the_fp32_parameter_trajectory():
 
 @pytest.mark.parametrize("M,K,N,r,G", [(32768, 320, 320, 128, 3), (8192, 640, 640, 128, 3), (2048, 1280, 1280, 128, 3),
                                        (616, 768, 640, 128, 2), (616, 768, 320, 128, 2), (512, 1280, 1280, 128, 3),
-                                       (4096, 320, 320, 32, 3), (1000, 64, 64, 32, 2)])
+                                       (4096, 320, 320, 32, 3), (1000, 64, 64, 32, 2)]
+                         + [s for r in (64, 256, 512) for s in ((32768, 320, 320, r, 3), (8192, 640, 640, r, 3), (2048, 1280, 1280, r, 3),
+                                                                (616, 768, 640, r, 2))])
 def test_grouped_lora_products_vs_fp64(M, K, N, r, G):
     """cl_gemm with grouped K segments (csrc/gemm.h a2_group_n / a1_group_n): G LoRACompatibleLinears that share their input
     (cldm/lora.py:285-291; to_q | to_k | to_v) as one forward launch, one u = [dy_g B_g] launch and one dx launch, vs fp64
     on the same bf16 values, at the production shapes of the three attention levels, the text-context projections
-    (M = 8 x 77), rank 32 (second segment below a 128-byte line) and a tiny ragged case."""
+    (M = 8 x 77), rank 32 (second segment below a 128-byte line) and a tiny ragged case; ranks 64 / 256 / 512 (the other shipped configs: the
+    group offset (n0 / a2_group_n) * K2 and the a1_group_n = r launch at other r than 128) with the up-projection at r^-1/2, i.e.
+    the low-rank branch at the magnitude of the main product."""
     _need_gpu()
     from ctrlora_amd import hip
     g = torch.Generator().manual_seed(M + N + r + G)
     bf = lambda *s, sc=1.0: _bf(torch.randn(*s, generator=g) * sc).cuda()
     x = bf(M, K)
-    W, A, Bm = bf(G * N, K, sc=K ** -0.5), bf(G * r, K, sc=K ** -0.5), bf(G * N, r, sc=0.05)
+    W, A, Bm = bf(G * N, K, sc=K ** -0.5), bf(G * r, K, sc=K ** -0.5), bf(G * N, r, sc=r ** -0.5 if r in (64, 256, 512) else 0.05)
     dy = bf(M, G * N, sc=0.1)
     t = torch.empty(M, G * r, dtype=torch.bfloat16, device="cuda")
     y = torch.empty(M, G * N, dtype=torch.bfloat16, device="cuda")
