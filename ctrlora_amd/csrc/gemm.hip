@@ -112,7 +112,9 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, f32x4_t (&acc)[F
   constexpr int PASSES = (FM + 1) / 2;
   constexpr int FPP = (FM >= 2) ? 2 : 1;  // m-frags per pass
   constexpr int ITERS = (FPP * 16 + RPI - 1) / RPI;
-  const EpiArgs e = epi_of(p);
+  EpiArgs e = epi_of(p);
+  // atomic split-K: every split adds its partial product onto C; bias, row-bias and residual enter once, with split 0
+  if (p.atomic && zsplit > 0) { e.bias = nullptr; e.rowbias = nullptr; e.residual = nullptr; }
   // PAIR: the two waves of a tile row (wn = 0: value columns, wn = 1: gate columns) combine for GEGLU
   const bool geglu = PAIR && p.act == ACT_GEGLU && !slab;
 #pragma unroll
@@ -1185,6 +1187,13 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
 template <typename T>
 static int launch_t_cfg(const GemmParams& p, hipStream_t stream, int cfg) {
   if (p.act == ACT_GEGLU && cfg != 2 && cfg != 12 && cfg != 8 && cfg != 10 && cfg != 14 && cfg != 16 && cfg != 18 && cfg != 20 && cfg != 23 && cfg != 25 && cfg != 27 && cfg != 29 && cfg != 44 && !((cfg == 40 || cfg == 47) && sizeof(T) == 2)) cfg = -2;   // needs a 2 x 80-column wave pair (40: in-register pairing)
+  if (p.act == ACT_GEGLU && cfg >= 0 && cfg != 2 && cfg != 23 && cfg != 44) {
+    // the full-line forms fall back to the generic 128 x 128 tile when K is not whole 128-byte lines (25 .. 30: or the operand is
+    // not linear): that tile has no value | gate wave pair and would store all N columns into C[M, N / 2].  The generic
+    // 160-wide tile takes these.
+    const int kps = 128 / (int)sizeof(T);
+    if (p.K1 % kps || p.K2 % kps || p.mode != GEMM_LINEAR) cfg = 2;
+  }
   if constexpr (sizeof(T) == 2) {
     // No table entry and no forced configuration: the x-stationary kernel by RULE where the measured table took it at the
     // benchmarked batch sizes (profiles/r05_gemm_xs/autotune_xs.out) -- other batch sizes (pre-training at the reference's
@@ -1382,6 +1391,8 @@ int launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
   if (p.mode != GEMM_LINEAR && !p.zero_page) return CL_EINVAL;
   if (p.K2 && (!p.A2 || !p.W2)) return CL_EINVAL;
   if (p.atomic == 0 && p.splitk > 1) return CL_EINVAL;
+  if (p.atomic && p.splitk > 1 && p.act != ACT_NONE) return CL_EINVAL;   // an activation of partial sums is not the activation of the sum
+  if (p.mode != GEMM_LINEAR && p.K2) return CL_EINVAL;                   // a second K segment exists for linear operands only
   if (p.rowbias && p.rows_per_batch <= 0) return CL_EINVAL;
   if (p.act == ACT_GEGLU && (p.N % 160 || p.rowbias || p.residual || p.atomic || p.alpha != 1.0f)) return CL_EINVAL;
   t_tag = tag_for(p, dtype);

@@ -131,6 +131,19 @@ typedef struct cl_gemm_params {
    * ln_stats (may be NULL): [M][2] fp32 {mean, rstd} for cl_layernorm_bwd.  bf16, linear mode, K1 in {320, 640}, K2 = 0,
    * no rowbias / residual only -- CL_EINVAL otherwise (the caller then runs cl_layernorm_fwd itself). */
   const float* ln_gamma; const float* ln_beta; float ln_eps; float* ln_stats;
+  /* Argument restrictions (CL_EINVAL otherwise; checked before any tile configuration is chosen, so they hold for every
+   * configuration alike -- tests/test_gpu_gemm_conformance.py):
+   *   - N % 8 == 0 and ldc % 8 == 0 (outputs are stored as whole 8-element vectors); K1 > 0;
+   *   - K1 and K2 multiples of 32 (bf16) / 16 (fp32): one 64-byte substep row;
+   *   - splitk > 1 only with atomic (without it the split factor is the library's choice); with atomic and splitk > 1 no
+   *     activation (act == 0): every split adds its partial product, bias / rowbias / residual enter once;
+   *   - rowbias needs rows_per_batch > 0; conv modes need zero_page;
+   *   - act 2 (GEGLU): N % 160 == 0, no rowbias, no residual, no atomic, alpha == 1 and alpha_n == 0;
+   *   - a second K segment (K2 > 0) and grouped segments exist in CL_GEMM_LINEAR only;
+   *   - alpha_n a multiple of 8 in [0, N]; a group width divides N, a2_group_n needs K2 > 0, and some tile width (64, 128
+   *     or 160 columns) must divide every group width: a tile never straddles two groups.
+   * rowbias and residual are read in `dtype` ([M / rows_per_batch, N] and [M, N]); with atomic, C is fp32 and the product is
+   * added onto what it holds. */
 } cl_gemm_params;
 
 /* Generic entry; the named operators below are thin fillers of cl_gemm_params. */

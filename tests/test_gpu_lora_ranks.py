@@ -24,6 +24,7 @@ import os
 import pytest
 import torch
 
+from tests.gemm_ref import TOL_F32, TOL_ONE_ROUNDING, _f32_gate, _rel, _tags
 from tests.util import GOLDEN, rel_l2
 from tests.test_gpu_bench_shapes import (BF16_EPS, BF16_GRAD_MAX, BF16_GRAD_MEDIAN, K_CMP, K_CMP_MAX, _bf, _comparator_vs, _need_gpu,
                                          _netcfg, _record)
@@ -31,60 +32,16 @@ from tests.test_gpu_bench_shapes import (BF16_EPS, BF16_GRAD_MAX, BF16_GRAD_MEDI
 pytestmark = pytest.mark.gpu
 
 RANKS = (64, 256, 512)
-# one bf16 rounding of the result (2^-9 = 1.95e-3 worst, ~1.7e-3 rms): test_grouped_lora_products_vs_fp64
-TOL_ONE_ROUNDING = 2.5e-3
+# (TOL_ONE_ROUNDING = 2.5e-3, one bf16 rounding of the result, and TOL_F32 = 2e-5, fp32-accumulated products of exact operands, live in
+# tests/gemm_ref.py with _tags, _rel and _f32_gate: the cl_gemm conformance suite shares them)
 # y / dx (5e-3) and dA / dB (8e-3) with the low-rank intermediate itself rounded to bf16: test_lora_fused_linear_production_shapes.
 # At these draws the contract (fp32 accumulation, t and u rounded to bf16, bf16 outputs) emulated on the CPU gives 2.0e-3 and
 # 1.7e-3 at every rank and shape; the last half-stage of t zeroed gives 0.25 .. 0.50
 TOL_Y, TOL_W = 5e-3, 8e-3
-# fp32-accumulated products of exact operands: test_grouped_weight_gradient_production_stage
-TOL_F32 = 2e-5
 
 SHAPES = [(32768, 320, 320), (8192, 640, 640), (2048, 1280, 1280), (32768, 320, 2560), (32768, 1280, 320), (8 * 77, 768, 320),
           (512, 1280, 1280), (8, 1280, 1280)]
 SQUARE = SHAPES[:3]
-
-
-class _tags:
-    """Launch tags (csrc/debug_hooks.h: cl_debug_gemm_tag) on, from an empty table, for the length of a `with` block."""
-
-    def __enter__(self):
-        from ctrlora_amd import hip
-        L = hip.lib()
-        assert L.cl_debug_gemm_tag_clear() == 0 and L.cl_debug_gemm_tag(1) == 0
-        return self
-
-    def __exit__(self, *exc):
-        from ctrlora_amd import hip
-        hip.lib().cl_debug_gemm_tag(0)
-        return False
-
-    @staticmethod
-    def restart():
-        from ctrlora_amd import hip
-        assert hip.lib().cl_debug_gemm_tag_clear() == 0
-
-    @staticmethod
-    def launches(**sig):
-        """(launches of the signatures that match, signatures in the table: 255 = the table is full and says nothing)."""
-        from ctrlora_amd import hip
-        tags = hip.gemm_tags()
-        return sum(t["launches"] for t in tags if all(t[k] == v for k, v in sig.items())), len(tags)
-
-
-def _rel(a, b):
-    """tests.util.rel_l2 without the trip to the host (operands of 32768 x 2560 in fp64)."""
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _f32_gate(got, ref64, a, b):
-    """(error, gate, error of torch's own fp32 product) for an fp32-accumulated product a @ b of exact operands: TOL_F32, or twice
-    the error of torch.matmul in fp32 on the same operands against the same fp64 reference where THAT is larger (the order of
-    32768 fp32 additions is not the kernel's to be blamed for)."""
-    e = _rel(got, ref64)
-    e_torch = _rel(a.float() @ b.float(), a.double() @ b.double())
-    return e, max(TOL_F32, 2 * e_torch), e_torch
 
 
 # ------------------------------------------------------------------------------ whole model, forward + backward, per rank
