@@ -65,6 +65,7 @@ int cl_debug_gemm_xs_rules(int on) { g_gemm_xs_rules = on ? 1 : 0; return CL_OK;
 int cl_debug_gemm_tag(int on) { g_gemm_tag_on = on ? 1 : 0; return CL_OK; }
 int cl_debug_gemm_tag_count(void) { return gemm_tag_count(); }
 int cl_debug_gemm_tag_clear(void) { gemm_tag_clear(); return CL_OK; }
+int cl_debug_gemm_config(int cfg, int* out10) { return gemm_config_get(cfg, out10); }
 int cl_debug_gemm_tag_get(int i, long* out12) { return out12 ? gemm_tag_get(i, out12) : CL_EINVAL; }
 
 int cl_gemm(const cl_gemm_params* p, int dtype, void* stream) {

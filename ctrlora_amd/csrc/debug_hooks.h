@@ -36,6 +36,12 @@ int cl_debug_gemm_tag_count(void);
 /* empties the launch-tag table (it holds 255 signatures: a process that tags several models in turn clears it between them) */
 int cl_debug_gemm_tag_clear(void);
 int cl_debug_gemm_tag_get(int i, long* out12);
+/* Read-only: the row of launch configuration `cfg` in the table every choice and dispatch of cl_gemm reads (csrc/gemm.hip: kCfgs).
+ * out[0..9] = id, family (0 gemm_kernel, 1 gemm_fl_kernel, 2 x-stationary, 3 loader / consumer), BM, BN, WGM, WGN (MFMA waves),
+ * KSUB (family 0), ring slots R, PRIO (family 1), flags: 1 persistent, 2 carries the GEGLU value | gate wave pair, 4 the same in bf16
+ * only, 8 falls back to configuration 1 unless K is whole 128-byte lines, 16 ... or the product is not linear, 32 ... or N % BN.
+ * CL_EINVAL for an id that has no row.  Touches no GPU. */
+int cl_debug_gemm_config(int cfg, int* out10);
 #ifdef __cplusplus
 }
 #endif

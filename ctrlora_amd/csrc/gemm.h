@@ -114,8 +114,9 @@ extern int g_gemm_force_splitk;   // tuning hook: > 0 imposes the split-K factor
 int gemm_tune_set(int dtype, int mode, int M, int N, int K1, int K2, int geglu, int cfg, int splitk);
 void gemm_tune_clear();
 int gemm_tune_size();
+int gemm_config_get(int cfg, int* out10);   // the row of a launch configuration (gemm.hip: kCfgs); CL_EINVAL for an id without one
 extern int g_gemm_force_cfg;   // tuning/probe hook (tile configuration override), -1 = heuristic
-extern int g_gemm_xs_rules;    // 1 = untabled signatures may take the x-stationary kernel by rule (gemm.hip: launch_t_cfg)
+extern int g_gemm_xs_rules;    // 1 = untabled signatures may take the x-stationary kernel by rule (gemm.hip: choose_cfg)
 // launch tags (csrc/debug_hooks.h: cl_debug_gemm_tag): extra, immediately exiting workgroups that name the product signature
 extern int g_gemm_tag_on;
 int gemm_cur_tag();                                   // tag of the product being launched on this thread (0 = tagging off)

@@ -39,6 +39,7 @@
 #include <type_traits>
 #include "gemm.h"
 #include <algorithm>
+#include <cstring>
 #include <map>
 #include <vector>
 #include <utility>
@@ -1151,7 +1152,7 @@ int g_gemm_force_splitk = 0;    // tuning hook: > 0 imposes the split-K factor (
 
 // Measured launch table (tools/gemm_autotune.py on an MI355X -> ctrlora_amd/gemm_tuned_gfx950.json, loaded by the host
 // at start-up): product signature -> (tile configuration, split-K factor).  A signature that is not in the table takes
-// the rules below; an entry can only name configurations the switch below accepts, each of which re-checks its own
+// the rules below; an entry can only name configurations of the table below (kCfgs), each of which re-checks its own
 // preconditions, so a stale or foreign table costs speed, never correctness.
 struct TuneKey {
   int v[7];   // dtype, mode, M, N, K1, K2, geglu
@@ -1159,8 +1160,117 @@ struct TuneKey {
 };
 static std::map<TuneKey, std::pair<int, int>> g_tune;
 
+// ---- tile configurations: what every launch id of cl_gemm IS, one row per id; the choice and the dispatch below read it all from here ----
+// Families: GEN = gemm_kernel (64-byte substeps, KSUB per step, R-slot ring); FL = gemm_fl_kernel (whole 128-byte K lines, R-slot ring; PRIO 0 plain,
+// 1 s_setprio(1) around the pure-MFMA half of every stage (+2-3 %), 2 split-issue (A-operand DMAs in MFMA batch 1, B-operand DMAs in batch 2),
+// 3 ping-pong (two wave groups one barrier apart, MFMA sections at priority 1), 4 coarse ping-pong (one L and one M section per stage));
+// XS = x-stationary kernel (gemm_xs.hip), W4 = loader / consumer kernel (gemm_w4.hip: the MFMA waves + 4 DMA waves) -- these two accept or
+// refuse a product themselves.  Flags: PERSIST = one launch of resident workgroups walks the tiles; PAIR = the 160-wide tile carries the
+// 2 x 80-column value | gate wave pair of GEGLU (PAIR_BF16: in bf16 only, paired in registers); K_LINES = runs as the row only where K1 and
+// K2 are whole 128-byte lines (conv modes: without K2), else as kFallbackId; LINEAR = ... and the product is linear; WHOLE_N = ... and N % BN == 0.
+enum CfgFam { GEN, FL, XS, W4 };
+enum CfgFlag { PERSIST = 1, PAIR = 2, PAIR_BF16 = 4, K_LINES = 8, LINEAR = 16, WHOLE_N = 32 };
+struct TileCfg { int id, fam, bm, bn, wgm, wgn, ksub, r, prio, flags; };
+constexpr int kFallbackId = 1;   // the generic 128 x 128 tile: takes every product
+constexpr TileCfg kCfgs[] = {
+  // id fam   BM   BN WGM WGN KSUB R PRIO flags
+  {  0, GEN,  64,  64, 2, 2, 1, 4, 0, 0},
+  {  1, GEN, 128, 128, 2, 2, 2, 4, 0, 0},
+  {  2, GEN, 128, 160, 2, 2, 2, 4, 0, PAIR},
+  {  3, GEN, 128, 160, 2, 2, 1, 4, 0, 0},
+  {  4, GEN, 128, 160, 2, 2, 2, 6, 0, 0},
+  {  5, GEN, 256, 160, 4, 2, 2, 4, 0, 0},
+  {  6, GEN, 128, 128, 2, 2, 1, 2, 0, 0},   // the round-0 structure, for A/B
+  {  7, GEN, 256, 128, 4, 2, 2, 4, 0, 0},
+  {  8, FL,  256, 160, 4, 2, 0, 3, 0, PAIR | K_LINES},
+  {  9, FL,  256, 128, 4, 2, 0, 3, 0, K_LINES},
+  // 128-row tiles, 4 waves, 2-slot ring: two workgroups per CU (small-K / mid-size products)
+  { 10, FL,  128, 160, 2, 2, 0, 2, 0, PAIR | K_LINES},
+  { 11, FL,  128, 128, 2, 2, 0, 2, 0, K_LINES},
+  { 12, FL,  256, 160, 4, 2, 0, 3, 1, PAIR | K_LINES},
+  { 13, FL,  256, 128, 4, 2, 0, 3, 1, K_LINES},
+  { 14, FL,  256, 160, 4, 2, 0, 3, 2, PAIR | K_LINES},
+  { 15, FL,  256, 128, 4, 2, 0, 3, 2, K_LINES},
+  { 16, FL,  256, 160, 4, 2, 0, 3, 3, PAIR | K_LINES},   // production
+  { 17, FL,  256, 128, 4, 2, 0, 3, 3, K_LINES},   // production
+  { 18, FL,  256, 160, 4, 2, 0, 3, 4, PAIR | K_LINES},
+  { 19, FL,  256, 128, 4, 2, 0, 3, 4, K_LINES},
+  // ping-pong on 128-row tiles (8 waves of 32 x 80 / 32 x 64): mid-size products
+  { 20, FL,  128, 160, 4, 2, 0, 3, 3, PAIR | K_LINES},
+  { 21, FL,  128, 128, 4, 2, 0, 3, 3, K_LINES},
+  // small-M tiles of the generic kernel (8x8 / 16x16 levels, text-context projections): offered to the tuner
+  { 22, GEN,  64, 128, 2, 2, 1, 4, 0, 0},
+  { 23, GEN,  64, 160, 2, 2, 1, 4, 0, PAIR},
+  { 24, GEN, 128,  64, 2, 2, 1, 4, 0, 0},
+  // persistent forms of 16 / 17 / 20 / 21 / 10 / 11
+  { 25, FL,  256, 160, 4, 2, 0, 3, 3, PERSIST | PAIR | K_LINES | LINEAR},
+  { 26, FL,  256, 128, 4, 2, 0, 3, 3, PERSIST | K_LINES | LINEAR},
+  { 27, FL,  128, 160, 4, 2, 0, 3, 3, PERSIST | PAIR | K_LINES | LINEAR},
+  { 28, FL,  128, 128, 4, 2, 0, 3, 3, PERSIST | K_LINES | LINEAR},
+  { 29, FL,  128, 160, 2, 2, 0, 2, 0, PERSIST | PAIR | K_LINES | LINEAR},
+  { 30, FL,  128, 128, 2, 2, 0, 2, 0, PERSIST | K_LINES | LINEAR},
+  // 128 x 80 full-line tiles, 4 waves of 32 x 80 (2- / 3-slot ring): twice the workgroups of the 128 x 160 tile for the
+  // M = 2048 / 8192 products of the 16x16 / 32x32 levels (offered to the tuner)
+  { 31, FL,  128,  80, 4, 1, 0, 2, 0, K_LINES | LINEAR | WHOLE_N},
+  { 32, FL,  128,  80, 4, 1, 0, 3, 0, K_LINES | LINEAR | WHOLE_N},
+  // full-N 128 x 320 tiles (8 waves of 64 x 80, 2-slot ring, 112 KB of LDS): the K = 320 products of the 64x64 level
+  // (M = 32768: 256 workgroups) read x ONCE instead of once per 160-column tile -- they are bound by bytes, not MFMA
+  // (16.3 us against an 8.4 us HBM floor with two tiles per row block); offered to the tuner
+  { 33, FL,  128, 320, 2, 4, 0, 2, 0, K_LINES | LINEAR | WHOLE_N},
+  // wide-N / short-K linears, K in {320, 640} (+ 128), 32-column chunks; the launch table's split column carries its
+  // column-run count
+  { 34, XS,  128,  32, 4, 1, 0, 0, 0, 0},
+  // 64 x 80 full-line tiles, 4 waves of 16 x 80 (3- / 2-slot ring, 54 / 36 KB: two or three workgroups per CU): the M = 2048
+  // products of the 16x16 level (N = K = 1280) are 256 workgroups of 4 waves as 128 x 80 tiles -- one wave per SIMD, nothing
+  // to hide a stage's DMA / barrier latency behind (18 us for 6.7 GFLOP); 512 workgroups here (also the 3x3 convs of the
+  // 8x8 level, M = 512: 128 tiles x split-K instead of 16 tiles x 16 splits -- a quarter of the slabs)
+  { 35, FL,   64,  80, 4, 1, 0, 3, 0, K_LINES | WHOLE_N},
+  { 36, FL,   64,  80, 4, 1, 0, 2, 0, K_LINES | WHOLE_N},
+  // loader / consumer kernel, 256-row tiles; 47 / 48: one workgroup per CU walks the tiles (the next tile's loads and this tile's stores overlap)
+  { 40, W4,  256, 160, 4, 1, 0, 3, 0, PAIR_BF16 | K_LINES},
+  { 41, W4,  256, 128, 4, 1, 0, 3, 0, K_LINES},
+  // Round 6: the small generic tiles with an 8-slot ring (7 substeps of LDS-DMA in flight instead of 3).  The short-K /
+  // small-M launches run a near-constant ~1 us per pipeline step whatever their size: an LDS-DMA round trip under load is
+  // ~2000 cycles (profiles/r06_w4/), and a step can only be as short as round trip / (slots - 1).  Offered to the tuner.
+  { 42, GEN,  64,  64, 2, 2, 1, 8, 0, 0},
+  { 43, GEN,  64, 128, 2, 2, 1, 8, 0, 0},
+  { 44, GEN,  64, 160, 2, 2, 1, 8, 0, PAIR},
+  { 45, GEN, 128,  64, 2, 2, 1, 8, 0, 0},
+  { 46, GEN, 128, 128, 2, 2, 2, 8, 0, 0},
+  { 47, W4,  256, 160, 4, 1, 0, 3, 0, PERSIST | PAIR_BF16 | K_LINES},
+  { 48, W4,  256, 128, 4, 1, 0, 3, 0, PERSIST | K_LINES},
+};
+constexpr int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
+
+constexpr const TileCfg* find_cfg(int id) {
+  for (const TileCfg& c : kCfgs)
+    if (c.id == id) return &c;
+  return nullptr;
+}
+constexpr bool cfg_table_ok() {
+  for (int i = 0; i < kNumCfgs; ++i) {
+    const TileCfg& c = kCfgs[i];
+    const int f = c.flags;
+    if (i && c.id <= kCfgs[i - 1].id) return false;                                  // ids ascend: each is there once
+    if ((f & (PAIR | PAIR_BF16)) && c.bn != 160) return false;                       // the value | gate pair is 2 x 80 columns
+    if ((f & (LINEAR | WHOLE_N)) && !(f & K_LINES)) return false;
+    if ((f & PERSIST) && c.fam == FL && !(f & LINEAR)) return false;                 // gemm_fl_persist_kernel has a linear form only
+    if (c.fam == GEN ? (c.prio || !c.ksub || (f & ~PAIR)) : c.ksub) return false;    // the generic kernel takes every product
+    if ((c.fam == FL || c.fam == W4) && !(f & K_LINES)) return false;                // these kernels move whole lines
+  }
+  return find_cfg(kFallbackId)->flags == 0;
+}
+static_assert(cfg_table_ok(), "kCfgs: a row contradicts itself or an id appears twice");
+
+// probe hook (csrc/debug_hooks.h: cl_debug_gemm_config): the row of an id as its ten integers
+int gemm_config_get(int cfg, int* out) {
+  const TileCfg* c = find_cfg(cfg);
+  if (c && out) memcpy(out, c, sizeof(*c));
+  return c && out ? CL_OK : CL_EINVAL;
+}
+
 int gemm_tune_set(int dtype, int mode, int M, int N, int K1, int K2, int geglu, int cfg, int splitk) {
-  if (cfg < 0 || cfg > 48 || splitk < 0 || splitk > 64) return CL_EINVAL;
+  if (cfg < 0 || cfg > kCfgs[kNumCfgs - 1].id || splitk < 0 || splitk > 64) return CL_EINVAL;
   g_tune[TuneKey{{dtype, mode, M, N, K1, K2, geglu ? 1 : 0}}] = std::make_pair(cfg, splitk);
   return CL_OK;
 }
@@ -1168,7 +1278,106 @@ void gemm_tune_clear() { g_tune.clear(); }
 int gemm_tune_size() { return (int)g_tune.size(); }
 
 template <typename T>
-static int launch_t_cfg(const GemmParams& p, hipStream_t stream, int cfg);
+static bool whole_lines(const GemmParams& p) { return p.K1 % (128 / (int)sizeof(T)) == 0 && p.K2 % (128 / (int)sizeof(T)) == 0; }
+
+// does this product miss what row c asks for (it then runs as kFallbackId)?
+template <typename T>
+static bool falls_back(const TileCfg& c, const GemmParams& p) {
+  if (!(c.flags & K_LINES)) return false;
+  if (!whole_lines<T>(p) || (p.mode != GEMM_LINEAR && ((c.flags & LINEAR) || p.K2))) return true;
+  return (c.flags & WHOLE_N) && p.N % c.bn;
+}
+
+// Which configuration runs this product?  cfg >= 0: forced or from the launch table; -1: the built-in rules; -2: the rules without the
+// x-stationary kernel.  The answer may be an id without a row, or -1 where no tile width fits the groups: the launch refuses both.
+template <typename T>
+static int choose_cfg(const GemmParams& p, int cfg) {
+  const bool lines = whole_lines<T>(p);
+  if (p.act == ACT_GEGLU && cfg >= 0) {
+    const TileCfg* c = find_cfg(cfg);
+    if (!c || !(c->flags & (sizeof(T) == 2 ? PAIR | PAIR_BF16 : PAIR))) cfg = -1;   // needs the value | gate wave pair
+    // kFallbackId has no such pair and would store all N columns into C[M, N / 2]: the generic 160-wide tile takes what a whole-line
+    // row would hand over to it (and, for these rows, every product that is not linear)
+    else if ((c->flags & K_LINES) && (!lines || p.mode != GEMM_LINEAR)) cfg = 2;
+  }
+  // No table entry and no forced configuration: the x-stationary kernel by RULE where the measured table took it at the
+  // benchmarked batch sizes (profiles/r05_gemm_xs/autotune_xs.out) -- other batch sizes (pre-training at the reference's
+  // batch 4: M = 16384 at the 64x64 level) have no entry of their own.  K = 320: N >= 320 from 16384 rows, N >= 1280 from 8192;
+  // K = 640: N >= 5120 from 8192 rows, N >= 640 from 32768.
+  if (sizeof(T) == 2 && cfg == -1 && g_gemm_xs_rules && p.mode == GEMM_LINEAR && p.act == ACT_NONE && !p.rowbias && !p.atomic &&
+      !p.out_f32 && !p.a1_group_n && (p.K2 == 0 || p.K2 == 128)) {
+    const bool k320 = p.K1 == 320 && p.N >= 320 && (p.M >= 16384 || (p.M >= 8192 && p.N >= 1280));   // (N = 128: the tuner kept the tiles)
+    const bool k640 = p.K1 == 640 && ((p.M >= 8192 && p.N >= 5120) || (p.M >= 32768 && p.N >= 640));
+    if (k320 || k640) return 34;
+  }
+  if (cfg < 0) {
+    // v2 (64-byte substeps, 4 waves) choices
+    if (p.M <= 64 || p.N <= 64) cfg = 0;
+    else if (p.N % 160 == 0) cfg = 2;
+    else cfg = 1;
+    if (cfg != 0 && (long)((p.M + 127) / 128) * ((p.N + 127) / 128) < 48 && p.atomic) cfg = 0;
+    // full-line 8-wave kernel: whenever K is whole 128-byte lines and the 256-row tile grid fills the
+    // chip, alone or with split-K at >= 8 stages per split (deep-K products of the 8x8 / 16x16 levels)
+    if (lines && !(p.mode != GEMM_LINEAR && p.K2) && !p.atomic && p.M > 128 && p.N >= 96) {
+      const int bn = (p.N % 160 == 0) ? 160 : 128;
+      const long t256 = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
+      const int steps = ((p.mode == GEMM_LINEAR ? 1 : 9) * p.K1 + p.K2) / (128 / (int)sizeof(T));
+      const long need = (256 + t256 - 1) / t256;   // split factor that fills 256 CUs
+      if (t256 >= 200 || (g_ws && steps >= 8 * need && (p.mode != GEMM_LINEAR || steps > 48)))
+        cfg = 16 + (bn == 160 ? 0 : 1);   // ping-pong schedule, 256-row tiles (split-K for the deep-K convs)
+      else if (p.mode == GEMM_LINEAR && steps <= 48 && (steps >= 16 || (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn) >= 128))
+        cfg = 20 + (bn == 160 ? 0 : 1);   // mid-size linears (16x16 / 32x32 levels): 128-row tiles fill the chip
+    }
+    if (p.act == ACT_GEGLU && cfg != 16 && cfg != 20) cfg = 2;
+  }
+  if (p.a1_group_n || p.a2_group_n) {
+    // grouped K segments (linear products): the tile width must divide every group width -- BN of the row that would actually run
+    // (a loader / consumer row that will refuse K not in whole lines counts as 128 wide, and so does an id without a row)
+    const TileCfg* c = find_cfg(cfg);
+    auto fits = [&](int bn) { return (!p.a1_group_n || p.a1_group_n % bn == 0) && (!p.a2_group_n || p.a2_group_n % bn == 0); };
+    if (!fits(c && !falls_back<T>(*c, p) ? c->bn : find_cfg(kFallbackId)->bn)) {
+      const bool big = p.M > 128 && lines && !p.atomic;
+      if (fits(160)) cfg = big ? (p.M >= 8192 ? 16 : 20) : 2;
+      else if (fits(128)) cfg = big ? (p.M >= 8192 ? 17 : 21) : 1;
+      else cfg = fits(64) ? 0 : -1;
+    }
+  }
+  return cfg;
+}
+
+template <typename T, int I>
+static int launch_row(const GemmParams& p, hipStream_t stream) {
+  constexpr TileCfg c = kCfgs[I];
+  if constexpr (c.fam == GEN) return launch_cfg<T, c.bm, c.bn, c.wgm, c.wgn, c.ksub, c.r>(p, stream);
+  else if constexpr (c.fam == FL) return launch_fl<T, c.bm, c.bn, c.wgm, c.wgn, c.r, c.prio, (c.flags & PERSIST) != 0>(p, stream);
+  else return CL_EINVAL;   // XS / W4: launch_t_cfg calls their launchers
+}
+
+// launch the GEN / FL row of an id, or kFallbackId where the product misses what the row asks for
+using AllRows = std::make_index_sequence<kNumCfgs>;
+template <typename T, size_t... I>
+static int launch_tile(int id, const GemmParams& p, hipStream_t stream, std::index_sequence<I...>) {
+  static constexpr int (*row[])(const GemmParams&, hipStream_t) = {&launch_row<T, (int)I>...};
+  const TileCfg* c = find_cfg(id);
+  if (!c) return CL_EINVAL;
+  return row[(falls_back<T>(*c, p) ? find_cfg(kFallbackId) : c) - kCfgs](p, stream);
+}
+
+template <typename T>
+static int launch_t_cfg(const GemmParams& p, hipStream_t stream, int cfg) {
+  const int id = choose_cfg<T>(p, cfg);
+  const TileCfg* c = find_cfg(id);
+  if (!c || c->fam == GEN || c->fam == FL) return launch_tile<T>(id, p, stream, AllRows{});
+  // The kernels of the other translation units (bf16) accept or refuse a product themselves: CL_EINVAL (an epilogue or a shape one
+  // does not cover; gemm_w4 also after it has picked a split) hands the product to the rules.
+  const bool by_rule = cfg < 0;   // x-stationary by rule: its launcher picks the column runs, and the rules do not ask it twice
+  int rc = CL_EINVAL;
+  if constexpr (sizeof(T) == 2)
+    rc = c->fam == XS ? launch_gemm_xs(p, stream, by_rule ? 0 : t_force_sk) : launch_gemm_w4(p, stream, c->bn, c->flags & PERSIST);
+  if (rc != CL_EINVAL) return rc;
+  if (c->fam == XS && !by_rule) t_force_sk = 0;   // (the table's split column was a run count, not a K split)
+  return launch_t_cfg<T>(p, stream, by_rule ? -2 : -1);
+}
 
 template <typename T>
 static int launch_t(const GemmParams& p, hipStream_t stream) {
@@ -1182,205 +1391,6 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
   const int rc = launch_t_cfg<T>(p, stream, cfg);
   t_force_sk = 0;
   return rc;
-}
-
-template <typename T>
-static int launch_t_cfg(const GemmParams& p, hipStream_t stream, int cfg) {
-  if (p.act == ACT_GEGLU && cfg != 2 && cfg != 12 && cfg != 8 && cfg != 10 && cfg != 14 && cfg != 16 && cfg != 18 && cfg != 20 && cfg != 23 && cfg != 25 && cfg != 27 && cfg != 29 && cfg != 44 && !((cfg == 40 || cfg == 47) && sizeof(T) == 2)) cfg = -2;   // needs a 2 x 80-column wave pair (40: in-register pairing)
-  if (p.act == ACT_GEGLU && cfg >= 0 && cfg != 2 && cfg != 23 && cfg != 44) {
-    // the full-line forms fall back to the generic 128 x 128 tile when K is not whole 128-byte lines (25 .. 30: or the operand is
-    // not linear): that tile has no value | gate wave pair and would store all N columns into C[M, N / 2].  The generic
-    // 160-wide tile takes these.
-    const int kps = 128 / (int)sizeof(T);
-    if (p.K1 % kps || p.K2 % kps || p.mode != GEMM_LINEAR) cfg = 2;
-  }
-  if constexpr (sizeof(T) == 2) {
-    // No table entry and no forced configuration: the x-stationary kernel by RULE where the measured table took it at the
-    // benchmarked batch sizes (profiles/r05_gemm_xs/autotune_xs.out) -- other batch sizes (pre-training at the reference's
-    // batch 4: M = 16384 at the 64x64 level) have no entry of their own.  K = 320: N >= 320 from 16384 rows, N >= 1280 from 8192;
-    // K = 640: N >= 5120 from 8192 rows, N >= 640 from 32768.  CL_EINVAL (an epilogue it does not cover) falls through.
-    if (cfg == -1 && g_gemm_xs_rules && p.mode == GEMM_LINEAR && p.act == ACT_NONE && !p.rowbias && !p.atomic && !p.out_f32 &&
-        !p.a1_group_n && (p.K2 == 0 || p.K2 == 128)) {
-      const bool k320 = p.K1 == 320 && p.N >= 320 && (p.M >= 16384 || (p.M >= 8192 && p.N >= 1280));   // (N = 128: the tuner kept the tiles)
-      const bool k640 = p.K1 == 640 && ((p.M >= 8192 && p.N >= 5120) || (p.M >= 32768 && p.N >= 640));
-      if (k320 || k640) {
-        const int rc = launch_gemm_xs(p, stream, 0);
-        if (rc != CL_EINVAL) return rc;
-      }
-    }
-  }
-  if (cfg < 0) {
-    // v2 (64-byte substeps, 4 waves) choices
-    if (p.M <= 64 || p.N <= 64) cfg = 0;
-    else if (p.N % 160 == 0) cfg = 2;
-    else cfg = 1;
-    if (cfg != 0 && (long)((p.M + 127) / 128) * ((p.N + 127) / 128) < 48 && p.atomic) cfg = 0;
-    // full-line 8-wave kernel: whenever K is whole 128-byte lines and the 256-row tile grid fills the
-    // chip, alone or with split-K at >= 8 stages per split (deep-K products of the 8x8 / 16x16 levels)
-    const int kps = 128 / (int)sizeof(T);
-    const bool fl_ok = p.K1 % kps == 0 && p.K2 % kps == 0 && !(p.mode != GEMM_LINEAR && p.K2) && !p.atomic &&
-                       p.M > 128 && p.N >= 96;
-    if (fl_ok) {
-      const int bn = (p.N % 160 == 0) ? 160 : 128;
-      const long t256 = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
-      const int steps = ((p.mode == GEMM_LINEAR ? 1 : 9) * p.K1 + p.K2) / kps;
-      const long need = (256 + t256 - 1) / t256;   // split factor that fills 256 CUs
-      if (t256 >= 200 || (g_ws && steps >= 8 * need && (p.mode != GEMM_LINEAR || steps > 48)))
-        cfg = 16 + (bn == 160 ? 0 : 1);   // ping-pong schedule, 256-row tiles (split-K for the deep-K convs)
-      else if (p.mode == GEMM_LINEAR && steps <= 48 && (steps >= 16 || (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn) >= 128))
-        cfg = 20 + (bn == 160 ? 0 : 1);   // mid-size linears (16x16 / 32x32 levels): 128-row tiles fill the chip
-    }
-    if (p.act == ACT_GEGLU && cfg != 16 && cfg != 20) cfg = 2;
-  }
-  if (p.a1_group_n || p.a2_group_n) {
-    // grouped K segments: the tile width must divide every group width.  BN of the configuration that would actually run
-    // (the full-line forms fall back to the generic 128 x 128 tile when K is not whole 128-byte lines)
-    const int kps = 128 / (int)sizeof(T);
-    const bool lines = p.K1 % kps == 0 && p.K2 % kps == 0;
-    auto bn_of = [&](int c) {
-      switch (c) {
-        case 0: case 24: case 42: case 45: return 64;
-        case 43: return 128;
-        case 44: return 160;
-        case 46: return 128;
-        case 1: case 6: case 7: case 22: return 128;
-        case 2: case 3: case 4: case 5: case 23: return 160;
-        case 40: case 47: return lines ? 160 : 128;
-        case 41: case 48: return 128;
-        case 31: case 32: case 35: case 36: return (lines && p.N % 80 == 0) ? 80 : 128;
-        case 33: return (lines && p.N % 320 == 0) ? 320 : 128;
-        case 34: return 32;    // x-stationary kernel: 32-column chunks (its own launcher re-checks the groups)
-        default: return lines ? ((c == 8 || c == 12 || c == 14 || c == 16 || c == 18 || c == 20 || c == 10 || c == 25 || c == 27 || c == 29) ? 160 : 128) : 128;
-      }
-    };
-    auto fits = [&](int bn) { return (!p.a1_group_n || p.a1_group_n % bn == 0) && (!p.a2_group_n || p.a2_group_n % bn == 0); };
-    if (!fits(bn_of(cfg))) {
-      const bool big = p.M > 128 && lines && !p.atomic;
-      if (fits(160)) cfg = big ? (p.M >= 8192 ? 16 : 20) : 2;
-      else if (fits(128)) cfg = big ? (p.M >= 8192 ? 17 : 21) : 1;
-      else if (fits(64)) cfg = 0;
-      else return CL_EINVAL;
-    }
-  }
-  switch (cfg) {
-    case 0: return launch_cfg<T, 64, 64, 2, 2, 1, 4>(p, stream);
-    case 1: return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-    case 2: return launch_cfg<T, 128, 160, 2, 2, 2, 4>(p, stream);
-    case 3: return launch_cfg<T, 128, 160, 2, 2, 1, 4>(p, stream);
-    case 4: return launch_cfg<T, 128, 160, 2, 2, 2, 6>(p, stream);
-    case 5: return launch_cfg<T, 256, 160, 4, 2, 2, 4>(p, stream);
-    case 6: return launch_cfg<T, 128, 128, 2, 2, 1, 2>(p, stream);   // the round-0 structure, for A/B
-    case 7: return launch_cfg<T, 256, 128, 4, 2, 2, 4>(p, stream);
-    case 8: case 9: {
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 8 ? launch_fl<T, 256, 160, 4, 2, 3>(p, stream) : launch_fl<T, 256, 128, 4, 2, 3>(p, stream);
-    }
-    case 12: case 13: {   // cfg 8 / 9 with s_setprio(1) around the pure-MFMA half of every stage (+2-3 %)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 12 ? launch_fl<T, 256, 160, 4, 2, 3, 1>(p, stream) : launch_fl<T, 256, 128, 4, 2, 3, 1>(p, stream);
-    }
-    case 14: case 15: {   // split-issue schedule (A-operand DMAs in MFMA batch 1, B-operand DMAs in batch 2)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 14 ? launch_fl<T, 256, 160, 4, 2, 3, 2>(p, stream) : launch_fl<T, 256, 128, 4, 2, 3, 2>(p, stream);
-    }
-    case 16: case 17: {   // production: ping-pong schedule: two wave groups one barrier apart, MFMA sections at priority 1
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 16 ? launch_fl<T, 256, 160, 4, 2, 3, 3>(p, stream) : launch_fl<T, 256, 128, 4, 2, 3, 3>(p, stream);
-    }
-    case 18: case 19: {   // coarse ping-pong (one L and one M section per stage)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 18 ? launch_fl<T, 256, 160, 4, 2, 3, 4>(p, stream) : launch_fl<T, 256, 128, 4, 2, 3, 4>(p, stream);
-    }
-    case 20: case 21: {   // ping-pong on 128-row tiles (8 waves of 32 x 80 / 32 x 64): mid-size products
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 20 ? launch_fl<T, 128, 160, 4, 2, 3, 3>(p, stream) : launch_fl<T, 128, 128, 4, 2, 3, 3>(p, stream);
-    }
-    case 10: case 11: {   // 128-row tiles, 4 waves, 2-slot ring: two workgroups per CU (small-K / mid-size products)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2))
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 10 ? launch_fl<T, 128, 160, 2, 2, 2>(p, stream) : launch_fl<T, 128, 128, 2, 2, 2>(p, stream);
-    }
-    case 25: case 26: case 27: case 28: case 29: case 30: {   // persistent forms of 16 / 17 / 20 / 21 / 10 / 11 (linear products)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || p.mode != GEMM_LINEAR)
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      switch (cfg) {
-        case 25: return launch_fl<T, 256, 160, 4, 2, 3, 3, true>(p, stream);
-        case 26: return launch_fl<T, 256, 128, 4, 2, 3, 3, true>(p, stream);
-        case 27: return launch_fl<T, 128, 160, 4, 2, 3, 3, true>(p, stream);
-        case 28: return launch_fl<T, 128, 128, 4, 2, 3, 3, true>(p, stream);
-        case 29: return launch_fl<T, 128, 160, 2, 2, 2, 0, true>(p, stream);
-        default: return launch_fl<T, 128, 128, 2, 2, 2, 0, true>(p, stream);
-      }
-    }
-    case 31: case 32: {   // 128 x 80 full-line tiles, 4 waves of 32 x 80 (2- / 3-slot ring): twice the workgroups of the
-      // 128 x 160 tile for the M = 2048 / 8192 products of the 16x16 / 32x32 levels (offered to the tuner)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || p.mode != GEMM_LINEAR || p.N % 80)
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 31 ? launch_fl<T, 128, 80, 4, 1, 2>(p, stream) : launch_fl<T, 128, 80, 4, 1, 3>(p, stream);
-    }
-    case 35: case 36: {   // 64 x 80 full-line tiles, 4 waves of 16 x 80 (3- / 2-slot ring, 54 / 36 KB: two or three workgroups per CU):
-      // the M = 2048 products of the 16x16 level (N = K = 1280) are 256 workgroups of 4 waves as 128 x 80 tiles -- one wave
-      // per SIMD, nothing to hide a stage's DMA / barrier latency behind (18 us for 6.7 GFLOP); 512 workgroups here
-      // (also the 3x3 convs of the 8x8 level, M = 512: 128 tiles x split-K instead of 16 tiles x 16 splits -- a quarter of the slabs)
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || (p.mode != GEMM_LINEAR && p.K2) || p.N % 80)
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return cfg == 35 ? launch_fl<T, 64, 80, 4, 1, 3>(p, stream) : launch_fl<T, 64, 80, 4, 1, 2>(p, stream);
-    }
-    case 33: {   // full-N 128 x 320 tiles (8 waves of 64 x 80, 2-slot ring, 112 KB of LDS): the K = 320 products of the 64x64 level
-      // (M = 32768: 256 workgroups) read x ONCE instead of once per 160-column tile -- they are bound by bytes, not MFMA
-      // (16.3 us against an 8.4 us HBM floor with two tiles per row block); offered to the tuner
-      const int kps = 128 / (int)sizeof(T);
-      if (p.K1 % kps || p.K2 % kps || p.mode != GEMM_LINEAR || p.N % 320)
-        return launch_cfg<T, 128, 128, 2, 2, 2, 4>(p, stream);
-      return launch_fl<T, 128, 320, 2, 4, 2>(p, stream);
-    }
-    case 34: {   // x-stationary streaming kernel (gemm_xs.hip): wide-N / short-K linears, K in {320, 640} (+ 128); the table's
-      // split column carries its column-run count.  Anything it does not cover takes the rules above.
-      if constexpr (sizeof(T) == 2) {
-        const int rc = launch_gemm_xs(p, stream, t_force_sk);
-        if (rc != CL_EINVAL) return rc;
-      }
-      t_force_sk = 0;
-      return launch_t_cfg<T>(p, stream, -1);
-    }
-    case 40: case 41: case 47: case 48: {   // loader / consumer kernel (gemm_w4.hip): 256 x 160 / 256 x 128 tiles, 4 MFMA waves + 4 DMA
-      // waves; 47 / 48: persistent (one workgroup per CU walks the tiles: the next tile's loads and this tile's stores overlap)
-      if constexpr (sizeof(T) == 2) {
-        const int rc = launch_gemm_w4(p, stream, (cfg == 40 || cfg == 47) ? 160 : 128, cfg >= 47);
-        if (rc != CL_EINVAL) return rc;
-      }
-      return launch_t_cfg<T>(p, stream, -1);
-    }
-    // Round 6: the same small tiles with an 8-slot ring (7 substeps of LDS-DMA in flight instead of 3).  The short-K / small-M
-    // launches run a near-constant ~1 us per pipeline step whatever their size: an LDS-DMA round trip under load is ~2000 cycles
-    // (profiles/r06_w4/), and a step can only be as short as round trip / (slots - 1).  Offered to the tuner.
-    case 42: return launch_cfg<T, 64, 64, 2, 2, 1, 8>(p, stream);
-    case 43: return launch_cfg<T, 64, 128, 2, 2, 1, 8>(p, stream);
-    case 44: return launch_cfg<T, 64, 160, 2, 2, 1, 8>(p, stream);
-    case 45: return launch_cfg<T, 128, 64, 2, 2, 1, 8>(p, stream);
-    case 46: return launch_cfg<T, 128, 128, 2, 2, 2, 8>(p, stream);
-    // small-M tiles of the generic kernel (8x8 / 16x16 levels, text-context projections): offered to the tuner
-    case 22: return launch_cfg<T, 64, 128, 2, 2, 1, 4>(p, stream);
-    case 23: return launch_cfg<T, 64, 160, 2, 2, 1, 4>(p, stream);
-    case 24: return launch_cfg<T, 128, 64, 2, 2, 1, 4>(p, stream);
-    default: return CL_EINVAL;
-  }
 }
 
 int launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
@@ -1407,22 +1417,14 @@ int launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
     } else if (p.M != 4 * mq || mq % 128 || p.Hout != 2 * p.Hin || p.Wout != 2 * p.Win) {
       return CL_EINVAL;
     }
-    const int bn = (p.N % 160 == 0) ? 160 : 128;
     // 128-row tiles (two workgroups per CU, split-K from the launcher's rule) measured 3-12 % ahead of 256-row tiles at every
     // production shape of all three modes (tools/time_conv_phase.py, profiles/r06_phase/time_conv_phase.log)
-    bool big = false;
-    if (g_gemm_force_cfg == 8 || g_gemm_force_cfg == 9) big = p.mode == GEMM_CONV_S2K4 || mq % 256 == 0;
-    if (g_gemm_force_cfg == 10 || g_gemm_force_cfg == 11) big = false;
-    const bool n160 = g_gemm_force_cfg >= 8 && g_gemm_force_cfg <= 11 ? (g_gemm_force_cfg % 2 == 0 && p.N % 160 == 0) : bn == 160;
+    const int f = g_gemm_force_cfg;
+    const bool big = (f == 8 || f == 9) && (p.mode == GEMM_CONV_S2K4 || mq % 256 == 0);
+    const bool n160 = p.N % 160 == 0 && !(f >= 8 && f <= 11 && f % 2);
+    const int id = (big ? 8 : 10) + (n160 ? 0 : 1);
     t_force_sk = g_gemm_force_splitk;
-    int rc;
-    if (dtype == CL_BF16) {
-      rc = big ? (n160 ? launch_fl<bf16_t, 256, 160, 4, 2, 3>(p, stream) : launch_fl<bf16_t, 256, 128, 4, 2, 3>(p, stream))
-               : (n160 ? launch_fl<bf16_t, 128, 160, 2, 2, 2>(p, stream) : launch_fl<bf16_t, 128, 128, 2, 2, 2>(p, stream));
-    } else {
-      rc = big ? (n160 ? launch_fl<float, 256, 160, 4, 2, 3>(p, stream) : launch_fl<float, 256, 128, 4, 2, 3>(p, stream))
-               : (n160 ? launch_fl<float, 128, 160, 2, 2, 2>(p, stream) : launch_fl<float, 128, 128, 2, 2, 2>(p, stream));
-    }
+    const int rc = dtype == CL_BF16 ? launch_tile<bf16_t>(id, p, stream, AllRows{}) : launch_tile<float>(id, p, stream, AllRows{});
     t_force_sk = 0;
     return rc;
   }

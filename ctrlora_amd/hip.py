@@ -128,6 +128,7 @@ _DEBUG_SIGS = {
     "cl_debug_gemm_tag_count": [],
     "cl_debug_gemm_tag_clear": [],
     "cl_debug_gemm_tag_get": [_I, _P],
+    "cl_debug_gemm_config": [_I, _P],
 }
 
 

@@ -50,7 +50,8 @@ int cl_set_workspace(void* device_ptr, long bytes);
 /* A second (third, fourth) scratch region bound to one stream: contractions launched on that stream use it
  * instead of the default, so concurrent streams never share split-K slabs. */
 int cl_set_stream_workspace(void* stream, void* device_ptr, long bytes);
-/* tuning hook: force a tile configuration of csrc/gemm.hip (-1 = built-in heuristic) */
+/* tuning hook: force a tile configuration (-1 = built-in heuristic).  The ids are the rows of the table kCfgs in
+ * csrc/gemm.hip: kernel family, tile, waves, ring, GEGLU wave pair, fall-back conditions, one line per id */
 int cl_gemm_force_config(int cfg);
 /* tuning hook: impose the split-K factor of the workspace path on every following contraction (0 = built-in rule) */
 int cl_gemm_force_splitk(int splitk);

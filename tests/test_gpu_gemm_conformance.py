@@ -290,7 +290,7 @@ def test_rule_dispatched_signature_elementwise_vs_fp64(b, sig, dtype):
 
 # ------------------------------------------------------------------------------------------------ C: every configuration
 
-# the cases of the switch in csrc/gemm.hip:launch_t_cfg
+# the ids csrc/gemm.hip launches (kept literal here: the rows of its table kCfgs are what this file tests)
 CONFIGS = tuple(range(0, 37)) + tuple(range(40, 49))
 NOT_CONFIGS = (37, 38, 39, 49)
 # (M, N, K1, K2): M in {1, 63, 129, 257, 1000}, N in {8, 72, 160, 328, 640}, K1 in {32, 96, 320, 1344} (96 and 1344 are not whole
