@@ -82,7 +82,9 @@ class ControlNet(nn.Module, EngineHost):
             from ctrlora_amd.engine import ControlNetE
             from ctrlora_amd.train import bind_trainables
             ex = ControlNetE(self._executor_state(), self.net_cfg(), self._engine_dtype(), self._device(),
-                             train_all=bool(getattr(self, "train_all_weights", False)))
+                             train_all=bool(getattr(self, "train_all_weights", False)),
+                             norm_trainable=bool(getattr(self, "norm_trainable", True)),
+                             zero_trainable=bool(getattr(self, "zero_trainable", True)))
             self.__dict__["_exec"] = ex
             self.__dict__["_bound"] = bind_trainables(self, ex)
         return ex

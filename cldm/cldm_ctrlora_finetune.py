@@ -31,6 +31,15 @@ def swap_linears(root: nn.Module, make_lora, skip=()):
     return out
 
 
+_REFERENCE_TOP_LEVEL = ("time_embed", "input_blocks", "zero_convs", "middle_block", "middle_block_out")
+
+
+def _reference_module_rank(name: str) -> int:
+    """Position of a parameter's top-level module in the reference ControlNet's registration order (stable sort key)."""
+    head = name.split(".", 1)[0]
+    return _REFERENCE_TOP_LEVEL.index(head) if head in _REFERENCE_TOP_LEVEL else len(_REFERENCE_TOP_LEVEL)
+
+
 class ControlNetFinetune(ControlNet):
     def __init__(self, ft_with_lora=True, lora_rank=128, norm_trainable=True, zero_trainable=True, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -96,7 +105,10 @@ class ControlFinetuneLDM(ControlLDM):
         """Name filter of :84-108 (LoRA layers; zero convs incl. middle_block_out; `norm` layers)."""
         cm = self.control_model
         names = []
-        for n, _ in cm.named_parameters():
+        # the reference registers time_embed and input_blocks BEFORE zero_convs (cldm/cldm.py:48-282), this mirror after:
+        # walk the top-level modules in the reference's order, so that the list (and the file configure_optimizers writes)
+        # comes out in its order
+        for n, _ in sorted(cm.named_parameters(), key=lambda kv: _reference_module_rank(kv[0])):
             assert "input_hint" not in n
             if not cm.ft_with_lora:
                 assert "lora_layer" not in n
@@ -112,15 +124,13 @@ class ControlFinetuneLDM(ControlLDM):
     def configure_optimizers(self):
         from ctrlora_amd.train import FusedAdamW
         cm = self.control_model
-        if cm.ft_with_lora and not (cm.zero_trainable and cm.norm_trainable):
-            raise NotImplementedError("the engine trains LoRA + zero convs + norm layers together "
-                                      "(every shipped config sets both flags)")
         names = self.trainable_names()
         os.makedirs("./tmp", exist_ok=True)
         with open("./tmp/finetune_trainable_params.txt", "w") as f:
             f.write("\n".join(names) + "\n")
         ex = cm.executor()
         bound = dict(zip([t.name for t in ex.tr.items], cm.__dict__["_bound"]))
+        # the executor was built with the same two flags (ControlNet.executor): its flat buffer holds exactly the filtered set
         assert set(names) == set(bound), "engine trainable set differs from the reference's name filter"
         params = [bound[n] for n in names]
         print(f"Optimizable params: {sum(p.numel() for p in params) / 1e6:.1f}M")

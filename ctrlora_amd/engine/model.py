@@ -26,12 +26,15 @@ class CtrLoRAEngine:
 
     def __init__(self, sd_unet: Dict[str, torch.Tensor], sd_controls: Sequence[Dict[str, torch.Tensor]], cfg: NetCfg,
                  dtype: torch.dtype = torch.bfloat16, device="cuda", need_bwd: bool = True,
-                 unet_prefix: str = "", control_prefix: str = ""):
+                 unet_prefix: str = "", control_prefix: str = "", norm_trainable: bool = True, zero_trainable: bool = True):
+        """norm_trainable / zero_trainable: ControlNetFinetune's switches, handed to every ControlNetE (off = those tensors
+        are frozen: not in the flat master / gradient buffer)."""
         hip.lib()   # fail loudly, before anything else, if the HIP library is missing
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.unet = UNetE(sd_unet, cfg, dtype, self.device, prefix=unet_prefix, need_bwd=need_bwd)
         self.controls: List[ControlNetE] = [
-            ControlNetE(sd, cfg, dtype, self.device, prefix=control_prefix, need_bwd=need_bwd) for sd in sd_controls]
+            ControlNetE(sd, cfg, dtype, self.device, prefix=control_prefix, need_bwd=need_bwd,
+                        norm_trainable=norm_trainable, zero_trainable=zero_trainable) for sd in sd_controls]
         self._rec = None
         self.cache_context_kv = False
         self._kv: Optional[dict] = None

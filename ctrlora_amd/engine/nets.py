@@ -72,9 +72,15 @@ def is_trainable_name(n: str) -> bool:
 
 class _Builder:
     def __init__(self, sd: Dict[str, torch.Tensor], prefix: str, dtype, device, need_bwd: bool,
-                 trainables: Optional[TrainableSet], lora_set: Optional[TrainableSet] = None, train_all: bool = False):
+                 trainables: Optional[TrainableSet], lora_set: Optional[TrainableSet] = None, train_all: bool = False,
+                 norm_trainable: bool = True, zero_trainable: bool = True):
         self.sd, self.prefix, self.dtype, self.device = sd, prefix, dtype, device
         self.need_bwd, self.tr = need_bwd, trainables
+        # ControlNetFinetune's switches (cldm_ctrlora_finetune.py:94-100): off = those tensors are never declared, so they
+        # are packed once like any frozen weight and no gradient, re-pack row or AdamW element exists for them.  Ignored
+        # under train_all (ft_with_lora=False trains every parameter, :101-104).
+        self.norm_trainable = bool(norm_trainable) or train_all
+        self.zero_trainable = bool(zero_trainable) or train_all
         # train_all (Base-ControlNet pre-training, cldm_ctrlora_pretrain.py:174-182): every weight / bias / norm of
         # the network is declared in `trainables`; the LoRA factors go to `lora_set` (one set per task bank)
         self.tr_lora = lora_set if lora_set is not None else trainables
@@ -127,7 +133,7 @@ class _Builder:
 
     def zero_conv(self, name: str) -> LinearW:
         L = LinearW(self._g(name + ".weight"), self._g(name + ".bias"), self.dtype, self.device, self.need_bwd)
-        if self.tr is not None:
+        if self.tr is not None and self.zero_trainable:
             tW = self.tr.declare(self.prefix + name + ".weight", self._g(name + ".weight").shape)
             tb = self.tr.declare(self.prefix + name + ".bias", self._g(name + ".bias").shape)
             L.attach_trainable_weight(tW, tb)
@@ -149,7 +155,7 @@ class _Builder:
 
     def norm(self, name: str) -> NormW:
         w = NormW(self._g(name + ".weight"), self._g(name + ".bias"), self.device)
-        if self.tr is not None and (self.train_all or is_trainable_name(name)):
+        if self.tr is not None and (self.train_all or (self.norm_trainable and is_trainable_name(name))):
             w.attach(self.tr.declare(self.prefix + name + ".weight", self._g(name + ".weight").shape),
                      self.tr.declare(self.prefix + name + ".bias", self._g(name + ".bias").shape))
         self.norms.append(w)
@@ -403,8 +409,11 @@ def _encoder_layers(b: _Builder, cfg: NetCfg, lora: bool, after_block=None):
 class ControlNetE:
     def __init__(self, sd, cfg: NetCfg, dtype, device, prefix: str = "", need_bwd: bool = True,
                  trainables: Optional[TrainableSet] = None, layout_only: bool = False, train_all: bool = False,
-                 lora_set: Optional[TrainableSet] = None, merge_lora: Optional[bool] = None):
-        """merge_lora (default: on for executors built without a backward): fold W + B A into one packed weight per
+                 lora_set: Optional[TrainableSet] = None, merge_lora: Optional[bool] = None,
+                 norm_trainable: bool = True, zero_trainable: bool = True):
+        """norm_trainable / zero_trainable = False (ControlNetFinetune's switches, LoRA fine-tuning only): the `norm` layers /
+        the zero convs (incl. middle_block_out) stay out of the flat master / gradient buffer and run as frozen weights.
+        merge_lora (default: on for executors built without a backward): fold W + B A into one packed weight per
         LoRA linear at every repack, as the reference's _fuse_lora does for inference (cldm/lora.py:297-318).
         layout_only: build the flat trainable layout (offsets, backward-ordered stage spans, the stage-completion
         hook) without packing anything for the kernels -- what the data-parallel exchange needs; usable without a
@@ -418,7 +427,8 @@ class ControlNetE:
         self.train_all = train_all
         # pre-training: base weights in self.tr, the active task's LoRA bank in self.tr_lora (switch_bank swaps it)
         self.tr_lora = (lora_set if lora_set is not None else TrainableSet()) if train_all else self.tr
-        b = _Builder(sd, prefix, dtype, device, need_bwd, self.tr, self.tr_lora, train_all)
+        b = _Builder(sd, prefix, dtype, device, need_bwd, self.tr, self.tr_lora, train_all, norm_trainable, zero_trainable)
+        self.norm_trainable, self.zero_trainable = b.norm_trainable, b.zero_trainable
         b.fold_lora = self.merge_lora
         self.lora = (prefix + "time_embed.0.lora_layer.down.weight") in sd
         self.time = _TimeEmbed(b, cfg)
@@ -487,9 +497,13 @@ class ControlNetE:
             self.repack()
 
     def backward_stage_order(self):
-        """Spans of flat_grad in the order the backward pass finalises them (what `_done` reports)."""
+        """Spans of flat_grad in the order the backward pass finalises them (what `_done` reports).  A stage that holds
+        no trainable (frozen zero convs: the input conv's and the Downsample stages, and every ResBlock-only stage whose
+        emb_layers factors moved to the tail) has no span and reports nothing -- the same on every rank, the layout being
+        a function of the architecture and the flags alone; the spans that remain still tile the buffer in order."""
         nb = len(self.blocks)
-        return [self.stage_spans[nb]] + [self.stage_spans[k] for k in range(nb - 1, -1, -1)] + [self.time_span]
+        order = [self.stage_spans[nb]] + [self.stage_spans[k] for k in range(nb - 1, -1, -1)] + [self.time_span]
+        return [s for s in order if s[1] > s[0]]
 
     def reload_frozen(self, sd):
         """module.load_state_dict() happened after this executor was built: refresh the packed frozen weights in
@@ -674,8 +688,9 @@ class ControlNetE:
 
     def _zero_bwd(self, ctx, k, h, dz, alpha, dh_in, B, HW, need_dx=True):
         z = self.zero[k]
-        dense_bwd_weight(ctx, z, h, dz, B, HW, alpha)
-        ctx.drop_transposes()
+        if z.tW is not None:      # a frozen zero conv (zero_trainable=False) passes the data gradient on, nothing else
+            dense_bwd_weight(ctx, z, h, dz, B, HW, alpha)
+            ctx.drop_transposes()
         if not need_dx:
             return None
         out = ctx.new(h.shape[0], z.K)

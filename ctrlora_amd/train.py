@@ -150,18 +150,28 @@ class FusedAdamW(torch.optim.Optimizer):
                     param_groups=[{k: v for k, v in g.items() if k != "params"} for g in self.param_groups])
 
     def load_state_dict(self, sd):
-        self._step_dev.fill_(int(sd["step"]))
         assert len(sd["m"]) == len(self._m), "optimizer state was saved for a different number of ControlNet banks"
+        # every check first: a refused state (e.g. a resume under other norm_trainable / zero_trainable flags) leaves this
+        # optimizer -- step counter included -- as it was
+        for key in ("m", "v"):
+            for ex, src in zip(self.executors, sd[key]):
+                if not isinstance(src, dict):
+                    continue
+                missing = [t.name for t in ex.tr.items if t.name not in src]
+                if missing:
+                    raise KeyError(f"optimizer state lacks {len(missing)} tensors, e.g. {missing[:3]}")
+                surplus = sorted(set(src) - set(ex.tr.by_name))
+                if surplus:
+                    raise KeyError(f"optimizer state holds {len(surplus)} tensors this model does not train, "
+                                   f"e.g. {surplus[:3]} (norm_trainable / zero_trainable differ from the checkpoint's?)")
         for key, bufs in (("m", self._m), ("v", self._v)):
             for ex, dst, src in zip(self.executors, bufs, sd[key]):
                 if isinstance(src, dict):
-                    missing = [t.name for t in ex.tr.items if t.name not in src]
-                    if missing:
-                        raise KeyError(f"optimizer state lacks {len(missing)} tensors, e.g. {missing[:3]}")
                     for t in ex.tr.items:
                         dst[t.offset:t.offset + t.master.numel()].copy_(src[t.name].reshape(-1))
                 else:       # rounds 1-3: ONE flat tensor in the flat buffer's order of the build that wrote it (no emb hoist)
                     _load_legacy_flat(ex, dst, src)
+        self._step_dev.fill_(int(sd["step"]))
         _restore_param_groups(self, sd)
 
 
