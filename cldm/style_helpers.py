@@ -6,7 +6,13 @@
   ip_adapter_state      (:114-129 change_key) IP-Adapter checkpoint keys -> the UNet's to_k_ip / to_v_ip: processor
                         indices 1, 3, ..., 31 go to the layers in order
   ip_scale_state        (:131-172 load_state_dict_ip) the per-layer ip_scale entries of the app's three targets
+  CLIPVisionEncoder     (:387-391) the IP-Adapter image encoder, CLIPVisionModelWithProjection, built from its config; on a GPU
+                        under no_grad it runs on the HIP engine (ctrlora_amd/engine/vit.py)
+  style_image_tokens    (:392-409) style image -> CLIPImageProcessor -> image_embeds -> ImageProjModel: the conditional and
+                        the unconditional (zero-embeds) tokens that go in as c_ip
 """
+import os
+from types import SimpleNamespace
 from typing import Dict, List
 
 import torch
@@ -60,3 +66,112 @@ def ip_adapter_state(ip_state: Dict[str, torch.Tensor], layer_names: List[str]) 
 def ip_scale_state(target: str, ip_scale: float, prefix: str = "model.diffusion_model.") -> Dict[str, torch.Tensor]:
     """The ip_scale entries load_state_dict_ip loads for `target` (one of IP_SCALE_TARGETS); other layers keep theirs."""
     return {f"{prefix}{b}.transformer_blocks.0.attn2.ip_scale": torch.tensor(ip_scale) for b in IP_SCALE_TARGETS[target]}
+
+
+# OpenCLIP ViT-H/14 in HF layout: the image encoder IP-Adapter for SD1.5 ships (its image_encoder/config.json)
+VIT_H_14 = dict(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=16, num_channels=3,
+                image_size=224, patch_size=14, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=1024)
+
+
+def _vision_config(config):
+    from transformers import CLIPVisionConfig
+    if config is None:
+        return CLIPVisionConfig(**VIT_H_14)
+    if isinstance(config, CLIPVisionConfig):
+        return config
+    if isinstance(config, dict):
+        return CLIPVisionConfig(**config)
+    if isinstance(config, (str, os.PathLike)) and os.path.isdir(config):       # an image_encoder/ directory: config.json only
+        import json
+        with open(os.path.join(config, "config.json")) as f:
+            d = json.load(f)
+        d = d.get("vision_config", d)
+        known = CLIPVisionConfig().to_dict()
+        return CLIPVisionConfig(**{k: v for k, v in d.items() if k in known and k not in ("model_type", "transformers_version")})
+    raise TypeError(f"config: a CLIPVisionConfig, a dict or a directory with config.json, not {type(config).__name__}")
+
+
+class CLIPVisionEncoder(nn.Module):
+    """CLIPVisionModelWithProjection under HF's own state-dict keys (`vision_model.*`, `visual_projection.weight`), so an
+    IP-Adapter image_encoder/ checkpoint loads with strict=True.  Built from a config (default: ViT-H/14), never from a hub
+    name: nothing is downloaded, the weights come from load_state_dict.  On a GPU under no_grad, with a config the executor
+    covers (ctrlora_amd/engine/vit.py: check_config), forward runs on the HIP engine in `engine_dtype` (bf16 unless
+    set_engine_dtype / CTRLORA_ENGINE_DTYPE says fp32); otherwise (CPU, autograd, other configs) it is the plain HF module."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        from transformers import CLIPVisionModelWithProjection
+        self.config = _vision_config(config)
+        hf = CLIPVisionModelWithProjection(self.config).eval()
+        self.vision_model, self.visual_projection = hf.vision_model, hf.visual_projection      # HF's keys, no extra prefix
+        self.__dict__["_hf"] = hf                                                              # (not a registered child)
+        self.engine_dtype = None
+        self.use_engine = True
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
+
+    def set_engine_dtype(self, dtype):
+        self.engine_dtype = dtype
+        self.invalidate_engine()
+
+    def invalidate_engine(self):
+        self.__dict__.pop("_vit", None)
+
+    def _refresh_engine(self):
+        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
+        ex = self.__dict__.get("_vit")
+        if ex is not None:
+            if ex.device != next(self.parameters()).device:
+                self.invalidate_engine()
+            else:
+                ex.load(self.state_dict())
+
+    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
+        self.invalidate_engine()
+        return super()._apply(fn, *args, **kwargs)
+
+    def engine(self):
+        ex = self.__dict__.get("_vit")
+        if ex is None:
+            from ctrlora_amd.engine.vit import ClipVisionE
+            dtype = self.engine_dtype
+            if dtype is None:
+                env = os.environ.get("CTRLORA_ENGINE_DTYPE", "bf16").lower()
+                dtype = torch.float32 if env in ("f32", "fp32", "float32") else torch.bfloat16
+            ex = ClipVisionE(self.state_dict(), self.config, dtype, next(self.parameters()).device)
+            self.__dict__["_vit"] = ex
+        return ex
+
+    def _on_engine(self, pixel_values):
+        from ctrlora_amd.engine.vit import supported
+        return (self.use_engine and pixel_values.is_cuda and not torch.is_grad_enabled() and supported(self.config)
+                and tuple(pixel_values.shape[1:]) == (self.config.num_channels, self.config.image_size, self.config.image_size))
+
+    def forward(self, pixel_values, output_hidden_states=False):
+        """An object with .image_embeds [B, projection_dim] (and .hidden_states when asked: HF's tuple from the plain module;
+        from the engine a tuple whose [-2] is the penultimate hidden state -- the one entry IP-Adapter-Plus reads -- and
+        None elsewhere)."""
+        if not self._on_engine(pixel_values):
+            return self._hf(pixel_values=pixel_values, output_hidden_states=output_hidden_states)
+        if not output_hidden_states:
+            return SimpleNamespace(image_embeds=self.engine().forward(pixel_values).clone(), hidden_states=None)
+        emb, pen = self.engine().forward(pixel_values, output_hidden_states=True)
+        hs = [None] * (self.config.num_hidden_layers + 1)
+        hs[-2] = pen.float()
+        return SimpleNamespace(image_embeds=emb.clone(), hidden_states=tuple(hs))
+
+
+def style_image_tokens(encoder, image_proj, images, processor=None):
+    """(tokens, uncond_tokens), each [B, clip_extra_context_tokens, cross_attention_dim]: what the app computes from the style
+    image (:392-409) -- processor(images).pixel_values -> encoder(...).image_embeds -> image_proj(embeds) and
+    image_proj(zeros_like(embeds)) -- ready to be passed as c_ip in cond / un_cond.  images: a PIL image or a uint8 HWC
+    array, or a list of them.  processor: a CLIPImageProcessor (default: CLIPImageProcessor())."""
+    if processor is None:
+        from transformers import CLIPImageProcessor
+        processor = CLIPImageProcessor()
+    dev = next(encoder.parameters()).device
+    pixel_values = processor(images=images, return_tensors="pt").pixel_values.to(dev)
+    with torch.no_grad():
+        embeds = encoder(pixel_values).image_embeds
+        pdt = next(image_proj.parameters()).dtype
+        embeds = embeds.to(device=next(image_proj.parameters()).device, dtype=pdt)
+        return image_proj(embeds), image_proj(torch.zeros_like(embeds))

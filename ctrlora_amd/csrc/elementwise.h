@@ -38,5 +38,9 @@ int colsum(int dtype, const void* in, long ldi, float* out, long ldo, int B, int
 int repack(int dtype, const float* flat, const long* desc, const int* tile_prefix, int ndesc, int total_tiles,
            hipStream_t st);
 int pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R, int C, int Cpad, hipStream_t st);
+// CLIPVisionEmbeddings: NCHW fp32 pixels -> zero-padded patch rows; class / patch rows + position embedding -> tokens
+int vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, hipStream_t st);
+int vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
+               int D, hipStream_t st);
 
 }  // namespace cl

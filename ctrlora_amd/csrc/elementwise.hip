@@ -517,7 +517,79 @@ __global__ void pack_kernel(const float* __restrict__ in, long ldi, T* __restric
   }
 }
 
+// ---------------------------------------------------------------- ViT patch rows / token assembly (CLIPVisionEmbeddings)
+// NCHW fp32 pixels [B, C, S, S] -> patch rows [B (S/P)^2, Kpad]: row (b, gy, gx), column (c, py, px) = pixel
+// (b, c, gy P + py, gx P + px), columns [C P P, Kpad) zero.  One lane per 8 output columns (one 16-byte store in bf16, two in
+// fp32); PAIR: P and S even, so columns (2j, 2j + 1) are neighbours of one pixel row at an 8-byte aligned address -- float2 loads.
+template <typename T, bool PAIR>
+__global__ void vit_patch_rows_kernel(const float* __restrict__ px, T* __restrict__ out, long ldo, int B, int C, int S, int P,
+                                      int Kpad) {
+  const int G = S / P, K = C * P * P, K8 = Kpad / 8;
+  const long n = (long)B * G * G * K8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / K8; const int k0 = (int)(i - row * K8) * 8;
+    const int b = (int)(row / (G * G)), g = (int)(row - (long)b * G * G), gy = g / G, gx = g - gy * G;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; e += PAIR ? 2 : 1) {
+      const int k = k0 + e;
+      const int c = k / (P * P), r = k - c * P * P, py = r / P, pxl = r - py * P;
+      const long src = (((long)b * C + c) * S + gy * P + py) * S + gx * P + pxl;
+      if constexpr (PAIR) {
+        const float2 t = k < K ? *reinterpret_cast<const float2*>(px + src) : make_float2(0.f, 0.f);   // (K even: a pair is whole)
+        v[e] = t.x; v[e + 1] = t.y;
+      } else {
+        v[e] = k < K ? px[src] : 0.f;
+      }
+    }
+    store8(out + row * ldo + k0, v);
+  }
+}
+
+// out[b, 0, :] = cls + pos[0];  out[b, 1 + i, :] = patch[b (T - 1) + i, :] + pos[1 + i]: fp32 add, one rounding to T
+template <typename T>
+__global__ void vit_tokens_kernel(const T* __restrict__ patch, long ldp, const float* __restrict__ cls,
+                                  const float* __restrict__ pos, T* __restrict__ out, long ldo, int B, int Tn, int D) {
+  const int D8 = D / 8;
+  const long n = (long)B * Tn * D8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / D8; const int c = (int)(i - row * D8) * 8;
+    const int b = (int)(row / Tn), t = (int)(row - (long)b * Tn);
+    float v[8], p[8];
+    if (t == 0) load8(cls + c, v);
+    else load8(patch + ((long)b * (Tn - 1) + t - 1) * ldp + c, v);
+    load8(pos + (long)t * D + c, p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += p[e];
+    store8(out + row * ldo + c, v);
+  }
+}
+
 // ================================================================= host launchers
+int vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, hipStream_t st) {
+  if (B < 1 || C < 1 || P < 1 || S < P || S % P || Kpad % 8 || Kpad < C * P * P || ldo < Kpad || ldo % 8) return CL_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(pixels) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return CL_EINVAL;
+  const int grid = ew_grid((long)B * (S / P) * (S / P) * (Kpad / 8));
+  const bool pair = P % 2 == 0 && S % 2 == 0;
+#define VIT_PR(T, PAIR) hipLaunchKernelGGL((vit_patch_rows_kernel<T, PAIR>), dim3(grid), dim3(256), 0, st, pixels, (T*)out, ldo, B, C, S, P, Kpad)
+  if (dtype == CL_BF16) { if (pair) VIT_PR(bf16_t, true); else VIT_PR(bf16_t, false); }
+  else if (dtype == CL_F32) { if (pair) VIT_PR(float, true); else VIT_PR(float, false); }
+  else return CL_EINVAL;
+#undef VIT_PR
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
+int vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
+               int D, hipStream_t st) {
+  if (B < 1 || T < 2 || D < 8 || D % 8 || ldp % 8 || ldo % 8 || ldp < D || ldo < D) return CL_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(patch) & 15) || (reinterpret_cast<uintptr_t>(cls) & 15) || (reinterpret_cast<uintptr_t>(pos) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & 15))
+    return CL_EINVAL;
+  const int grid = ew_grid((long)B * T * (D / 8));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((vit_tokens_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)patch, ldp, cls, pos, (bf16_t*)out, ldo, B, T, D);
+  else if (dtype == CL_F32) hipLaunchKernelGGL((vit_tokens_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)patch, ldp, cls, pos, (float*)out, ldo, B, T, D);
+  else return CL_EINVAL;
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
 int geglu_fwd(int dtype, const void* h, long ldh, void* out, long ldo, long M, int F, hipStream_t st) {
   if (F % 8 || ldh % 8 || ldo % 8) return CL_EINVAL;
   if (dtype == CL_BF16) hipLaunchKernelGGL((geglu_fwd_kernel<bf16_t>), dim3(ew_grid(M * (F / 8))), dim3(256), 0, st, (const bf16_t*)h, ldh, (bf16_t*)out, ldo, M, F);

@@ -38,7 +38,12 @@ enum GemmAct {
   ACT_GEGLU = 2,
   // The same fusion for the x-stationary kernel (gemm_xs.hip) ONLY: W's rows stay in their natural order [value (N / 2) | gate
   // (N / 2)] (attention.py:55: chunk(2, dim=-1)).  Needs K1 in {320, 640}, K2 in {0, 128}, N % 64 == 0; other kernels return CL_EINVAL.
-  ACT_GEGLU_SPLIT = 3
+  ACT_GEGLU_SPLIT = 3,
+  // Exact (erf) GELU of the fp32 accumulator + bias (+ rowbias), before alpha / residual: CLIPMLP's fc1 with hidden_act "gelu"
+  // (transformers/models/clip/modeling_clip.py: CLIPMLP.forward).  In the shared epilogue (gemm_epi.h: epilogue8), so every tile
+  // kernel and the split-K reduce apply it; the x-stationary and the loader / consumer kernels refuse it (CL_EINVAL: the rules
+  // then choose a tile kernel).  No atomic.
+  ACT_GELU = 4
 };
 
 struct GemmParams {

@@ -1405,6 +1405,8 @@ int launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
   if (p.mode != GEMM_LINEAR && p.K2) return CL_EINVAL;                   // a second K segment exists for linear operands only
   if (p.rowbias && p.rows_per_batch <= 0) return CL_EINVAL;
   if (p.act == ACT_GEGLU && (p.N % 160 || p.rowbias || p.residual || p.atomic || p.alpha != 1.0f)) return CL_EINVAL;
+  // exact GELU: applied by epilogue8 on the finished sum (directly, or in the split-K reduce); an atomic launch adds onto C
+  if (p.act == ACT_GELU && (p.atomic || p.ln_gamma)) return CL_EINVAL;
   t_tag = tag_for(p, dtype);
   if (gemm_phase_mode(p.mode) || p.mode == GEMM_CONV_S2K4) {
     // phase-decomposed UP2 / T2 and the 4x4 stride-2 window (gemm.h): the full-line kernel's generic-conv form only;

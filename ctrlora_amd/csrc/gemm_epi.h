@@ -1,5 +1,5 @@
 // Epilogue shared by the tile kernels (gemm.hip) and the loader / consumer kernel (gemm_w4.hip): bias, time-embedding
-// row-bias (openaimodel.py:272), SiLU, alpha / alpha_n, beta * residual (openaimodel.py:274, cldm/cldm.py:41), fp32 / bf16 /
+// row-bias (openaimodel.py:272), SiLU / exact GELU (ACT_GELU: epilogue8 only -- gemm_w4.hip refuses it), alpha / alpha_n, beta * residual (openaimodel.py:274, cldm/cldm.py:41), fp32 / bf16 /
 // atomic store -- applied to 8 consecutive columns of one output row.
 #pragma once
 #include "gemm.h"
@@ -36,6 +36,9 @@ __device__ __forceinline__ void epilogue8(const EpiArgs& e, float v[8], int grow
   if (e.act == ACT_SILU) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = silu_f(v[i]);
+  } else if (e.act == ACT_GELU) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = gelu_f(v[i]);
   }
   const float al = (e.alpha_n > 0 && gcol >= e.alpha_n) ? 1.0f : e.alpha;     // (8 columns never straddle alpha_n)
 #pragma unroll

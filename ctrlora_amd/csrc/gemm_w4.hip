@@ -977,6 +977,7 @@ int launch_gemm_w4(const GemmParams& p, hipStream_t stream, int bn, int persist)
   if (p.atomic || p.K1 % 64 || p.K2 % 64 || p.K1 <= 0) return CL_EINVAL;
   if (p.act == ACT_GEGLU && bn != 160) return CL_EINVAL;
   if (p.act == ACT_GEGLU_SPLIT || p.ln_gamma) return CL_EINVAL;
+  if (p.act == ACT_GELU) return CL_EINVAL;   // epilogue8_tail_bf16 has no GELU: the tile kernels take the product
   if (bn == 160) return launch_w4_nw<10>(p, stream, persist != 0);
   if (bn == 128) return launch_w4_nw<8>(p, stream, persist != 0);
   return CL_EINVAL;

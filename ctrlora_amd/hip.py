@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("CTRLORA_LIB") or os.path.join(_HERE, "libctrlora_hip.
 
 BF16, F32 = 0, 1
 LINEAR, CONV_S1, CONV_S2, CONV_UP2, CONV_T2, CONV_S2A, CONV_UP2P, CONV_T2P, CONV_S2K4 = 0, 1, 2, 3, 4, 5, 6, 7, 8
-ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GEGLU_SPLIT = 0, 1, 2, 3
+ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GEGLU_SPLIT, ACT_GELU = 0, 1, 2, 3, 4
 
 
 class HipError(RuntimeError):
@@ -99,6 +99,8 @@ _SIGS = {
     "cl_colsum": [_I, _P, _L, _P, _L, _I, _I, _I, _F, _P],
     "cl_pool2x2": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
     "cl_pack2d": [_I, _P, _L, _P, _L, _L, _I, _I, _P],
+    "cl_vit_patch_rows": [_I, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "cl_vit_tokens": [_I, _P, _L, _P, _P, _P, _L, _I, _I, _I, _P],
     "cl_repack": [_I, _P, _P, _P, _I, _I, _P],
     "cl_timestep_embedding": [_I, _P, _P, _P, _L, _I, _I, _P],
     "cl_qsample": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
@@ -558,6 +560,24 @@ def pack2d(src_f32, dst, Cpad=None):
     _chk(lib().cl_pack2d(dt(dst), src_f32.data_ptr(), ld(src_f32), dst.data_ptr(), ld(dst), R, C_,
                          dst.shape[1] if Cpad is None else Cpad, stream()), "cl_pack2d")
     return dst
+
+
+def vit_patch_rows(pixels, out, P):
+    """NCHW fp32 pixels [B, C, S, S] -> patch rows out [B (S/P)^2, Kpad] (columns (c, py, px), zero pad): cl_vit_patch_rows."""
+    B, C_, S, S2 = pixels.shape
+    assert S == S2 and pixels.dtype == torch.float32 and pixels.is_contiguous() and out.shape[0] == B * (S // P) ** 2
+    _chk(lib().cl_vit_patch_rows(dt(out), pixels.data_ptr(), out.data_ptr(), ld(out), B, C_, S, P, out.shape[1], stream()),
+         "cl_vit_patch_rows")
+    return out
+
+
+def vit_tokens(patch, cls, pos, out, B):
+    """out[b, 0] = cls + pos[0]; out[b, 1 + i] = patch[b (T - 1) + i] + pos[1 + i] (cls [D], pos [T, D] fp32): cl_vit_tokens."""
+    T, D = pos.shape
+    assert out.shape == (B * T, D) and patch.shape == (B * (T - 1), D) and cls.is_contiguous() and pos.is_contiguous()
+    _chk(lib().cl_vit_tokens(dt(out), patch.data_ptr(), ld(patch), cls.data_ptr(), pos.data_ptr(), out.data_ptr(), ld(out), B, T, D,
+                             stream()), "cl_vit_tokens")
+    return out
 
 
 def timestep_embedding(t_long, freqs, out):

@@ -111,7 +111,10 @@ typedef struct cl_gemm_params {
   int act;                            /* 0 none, 1 SiLU, 2 GEGLU (value / gate rows of W interleaved per 160-row tile, C is
                                          [M, N/2]: ldm/modules/attention.py:49-56 fused into the projection; no-grad forwards),
                                          3 (ABI 7) the same fusion with W's rows in their natural [value | gate] order:
-                                         bf16, K1 in {320, 640}, K2 in {0, 128}, N % 64 == 0 only -- CL_EINVAL otherwise   */
+                                         bf16, K1 in {320, 640}, K2 in {0, 128}, N % 64 == 0 only -- CL_EINVAL otherwise,
+                                         4 (added in ABI 7, compatible) exact GELU 0.5 x (1 + erf(x / sqrt 2)) of the fp32 sum
+                                         A1.W1^T [+ A2.W2^T] + bias [+ rowbias], before alpha and beta * residual: CLIPMLP.fc1 +
+                                         activation_fn (transformers/models/clip/modeling_clip.py:346-350, hidden_act "gelu") */
   void* C; long ldc;
   int out_f32;                        /* store fp32 regardless of dtype                      */
   int atomic;                         /* fp32 atomicAdd into C (gradient accumulation)       */
@@ -140,6 +143,10 @@ typedef struct cl_gemm_params {
    *     activation (act == 0): every split adds its partial product, bias / rowbias / residual enter once;
    *   - rowbias needs rows_per_batch > 0; conv modes need zero_page;
    *   - act 2 (GEGLU): N % 160 == 0, no rowbias, no residual, no atomic, alpha == 1 and alpha_n == 0;
+   *   - act 4 (GELU): no atomic, no LayerNorm prologue; the split factor stays the library's choice, and the activation is
+   *     applied to the reduced sum (in the split-K reduce), never per split.  Every tile configuration honours it in both
+   *     dtypes; a forced / tabled configuration of the x-stationary or the loader / consumer kernel hands the product to the
+   *     rules (those two kernels have no GELU epilogue), so no configuration returns an un-activated product;
    *   - a second K segment (K2 > 0) and grouped segments exist in CL_GEMM_LINEAR only;
    *   - alpha_n a multiple of 8 in [0, N]; a group width divides N, a2_group_n needs K2 > 0, and some tile width (64, 128
    *     or 160 columns) must divide every group width: a tile never straddles two groups.
@@ -289,6 +296,20 @@ int cl_tok_to_nchw(int dtype, const void* in, long ldi, float* out, int B, int C
 int cl_colsum(int dtype, const void* in, long ldi, float* out, long ldo, int B, int HW, int C, float scale, void* stream);
 int cl_pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, void* stream);
 int cl_pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R, int C, int Cpad, void* stream);
+/* CLIPVisionEmbeddings.forward (transformers/models/clip/modeling_clip.py:202-218, transformers 5.x), added in ABI 7 (compatible).
+ * cl_vit_patch_rows: NCHW fp32 pixel_values [B, C, S, S] -> patch rows [B (S/P)^2, Kpad] in `dtype` (row stride ldo); row
+ * (b, gy, gx), columns ordered (c, py, px) as nn.Conv2d's weight [hidden, C, P, P] flattens, columns [C P P, Kpad) zero
+ * (Kpad = C P P rounded up to the K granularity of cl_gemm, a multiple of 8: 588 -> 608).  The patch embedding -- a stride-P
+ * P x P convolution without bias (:148-154 patch_embedding) -- is then ONE CL_GEMM_LINEAR product against the zero-padded
+ * flattened weight.  S % P == 0; pixels and out 16-byte aligned.
+ * cl_vit_tokens: out[b, 0, :] = cls + pos[0], out[b, 1 + i, :] = patch[b (T - 1) + i, :] + pos[1 + i] (:212-217: the class
+ * embedding concatenated in front, + position_embedding): cls [D], pos [T, D] fp32, patch / out in `dtype`, the add in fp32,
+ * one rounding.  D % 8 == 0.  A launch of its own rather than an epilogue of the patch product: rowbias indexes by sample,
+ * not by token, and the class rows shift every sample's output rows, so the epilogue form would need a class-row kernel as
+ * well -- two launches either way, and this one leaves cl_gemm as it is. */
+int cl_vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, void* stream);
+int cl_vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
+                  int D, void* stream);
 /* One-launch refresh of the engine's storage-dtype copies of all trainable matrices from the flat fp32
  * master buffer after an optimizer step.  desc = device table of 8 longs per matrix {src offset in floats,
  * rows << 32 | cols, dst [rows][cols] or 0, dst^T [cols][rows] or 0, source row stride (0 = cols), dst row stride
