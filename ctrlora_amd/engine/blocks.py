@@ -7,6 +7,10 @@ block has an explicit `fwd` (optionally recording what its `bwd` needs) and a ha
 is recomputed (the algorithmic minimum, vs. the reference's
 checkpoint()-recompute + dead weight-gradients).
 
+The engine dtype picks one of two kernel families for attention and for weight gradients -- bf16: transpose-free kernels;
+fp32 (parity mode): kernels that read materialised, zero-padded transposes.  No block decides that: attention goes through
+hip.attention / hip.attention_backward, every weight gradient through Ctx.wgrad, and those build the fp32 family's scratch.
+
 Reference modules restated (behaviour, not code):
   ResBlock._forward                ldm/modules/diffusionmodules/openaimodel.py:254-274
   Downsample / Upsample            openaimodel.py:108-118,157-159
@@ -52,6 +56,20 @@ class Ctx:
         self._wq.append((dy, x, dW, scale, conv))  # keeps dy / x alive until the flush
         if len(self._wq) >= 24:
             self.flush_wgrad()
+
+    def wgrad(self, dy, x, dW, scale=1.0, conv=None):
+        """dW [N, K] (fp32) += scale * dy^T x, the ONE place that picks the weight-gradient kernel family.  bf16: queued for the
+        block's grouped transpose-free launch.  fp32 parity mode: explicit transposes, one launch now.
+        conv = (tap, Hin, Win, Ho, Wo, stride, pad): x is a 3x3 conv's NHWC input and dy lives on its output grid -- one tap of
+        the conv's weight gradient (fp32 materialises the shifted operand first)."""
+        if self.dtype == torch.bfloat16:
+            self.queue_wgrad(dy, x, dW, scale, conv)
+            return
+        if conv is not None:
+            tap, Hin, Win, Ho, Wo, stride, pad = conv
+            xs = self.new(dy.shape[0], x.shape[1])
+            x = hip.conv_tap_gather(x, xs, dy.shape[0] // (Ho * Wo), Hin, Win, Ho, Wo, tap, stride, pad)
+        hip.weight_grad(self.transposed(dy), self.transposed(x), dW, scale)
 
     def queue_bias_grad(self, dy, db, rows: int, scale: float = 1.0):
         """db += scale * column sums of dy: rides with the stage's weight-gradient group when that runs on the side stream."""
@@ -109,7 +127,7 @@ class Ctx:
             self._gn_ws = torch.empty(max(n, 1 << 20), dtype=torch.float32, device=self.device)
         return self._gn_ws
 
-    # transposed, zero-padded copy [C, Mp] of a [M, C] activation (weight-gradient operand);
+    # transposed, zero-padded copy [C, Mp] of a [M, C] activation (operand of the fp32 weight gradient, see wgrad);
     # cached for the lifetime of one block backward because q/k/v share their input.
     def transposed(self, x: torch.Tensor) -> torch.Tensor:
         key = (x.data_ptr(), x.shape[0], x.shape[1], x.stride(0))
@@ -146,6 +164,12 @@ def linear_fwd(ctx: Ctx, L: LinearW, x, out=None, residual=None, act=hip.ACT_NON
     hip.gemm(x, L.Wm if merged else L.W, out, a2=t, w2=L.B if t is not None else None, bias=L.bias, residual=residual,
              alpha=alpha, beta=beta if residual is not None else 0.0, act=act, out_f32=out_f32, alpha_n=alpha_n, ln=ln)
     return out, t
+
+
+def input_live(ctx: Ctx, L: LinearW) -> bool:
+    """Is the tensor L's product reads an operand of something else too -- t = x A^T of an unmerged LoRA, or the weight gradient
+    of a dense weight that trains (pre-training / ft_with_lora = False)?  Then a LayerNorm in front of it must be materialised."""
+    return (bool(L.r) and not (L.Wm is not None and not ctx.record)) or (ctx.record and L.tW is not None)
 
 
 def ln_prologue_ok(ctx: Ctx, M: int, N: int, K: int, lora_live: bool, act=hip.ACT_NONE) -> bool:
@@ -187,12 +211,8 @@ def linear_bwd_lora(ctx: Ctx, L: LinearW, x, t, dy, u):
     """dB += dy^T t ;  dA += u^T x   (fp32, split-K atomics into the flat gradient buffer)."""
     if not L.r:
         return
-    if ctx.dtype == torch.bfloat16:      # transpose-free kernel (LDS transpose reads), grouped per block
-        ctx.queue_wgrad(dy, t, L.tB.grad)
-        ctx.queue_wgrad(u, x, L.tA.grad)
-        return
-    hip.weight_grad(ctx.transposed(dy), ctx.transposed(t), L.tB.grad)
-    hip.weight_grad(ctx.transposed(u), ctx.transposed(x), L.tA.grad)
+    ctx.wgrad(dy, t, L.tB.grad)
+    ctx.wgrad(u, x, L.tA.grad)
 
 
 def base_bwd_weight(ctx: Ctx, L: LinearW, x, dy):
@@ -223,22 +243,13 @@ def conv3_bwd_weight(ctx: Ctx, cw: Conv3W, x, dy, B, Hin, Win, mode=hip.CONV_S1)
         hip.colsum(dy, cw.tb.grad.view(1, cw.O), 1, dy.shape[0], 1.0)
         return
     for t in range(9):
-        gs = g[:, t * cw.Ip:(t + 1) * cw.Ip]
-        if ctx.dtype == torch.bfloat16:
-            ctx.queue_wgrad(dy, x, gs, 1.0, conv=(t, Hin, Win, Ho, Wo, stride, 1))
-        else:     # fp32 parity mode: materialise the shifted operand, explicit transposes
-            xs = ctx.new(B * Ho * Wo, cw.Ip)
-            hip.conv_tap_gather(x, xs, B, Hin, Win, Ho, Wo, t, stride, 1)
-            hip.weight_grad(ctx.transposed(dy), ctx.transposed(xs), gs)
+        ctx.wgrad(dy, x, g[:, t * cw.Ip:(t + 1) * cw.Ip], 1.0, conv=(t, Hin, Win, Ho, Wo, stride, 1))
     hip.colsum(dy, cw.tb.grad.view(1, cw.O), 1, dy.shape[0], 1.0)
 
 
 def dense_bwd_weight(ctx: Ctx, L: LinearW, x, dy, B: int, HW: int, scale: float = 1.0):
     """Trainable dense 1x1 conv (zero convs): dW += scale * dy^T x ; db += scale * colsum(dy)."""
-    if ctx.dtype == torch.bfloat16:
-        ctx.queue_wgrad(dy, x, L.tW.grad.view(L.N, L.K), scale)
-    else:
-        hip.weight_grad(ctx.transposed(dy), ctx.transposed(x), L.tW.grad.view(L.N, L.K), scale)
+    ctx.wgrad(dy, x, L.tW.grad.view(L.N, L.K), scale)
     if L.tb is not None:
         ctx.queue_bias_grad(dy, L.tb.grad.view(1, L.N), B * HW, scale)
 
@@ -281,6 +292,15 @@ class LayerNormOp:
         (mean, rstd) only when a backward pass will want them."""
         stats = torch.empty((rows, 2), dtype=torch.float32, device=ctx.device) if ctx.record else None
         return (self.w.gamma, self.w.beta, self.eps, stats)
+
+    def feed(self, ctx: Ctx, x, fused: bool):
+        """The norm in front of a product: (rows to feed the product, stats, ln).  fused -- the caller's ln_fusable /
+        ln_prologue_ok verdict: the product normalises its own rows, so x goes in as it is with ln = prologue();
+        otherwise the norm runs here and ln is None."""
+        if fused:
+            ln = self.prologue(ctx, x.shape[0])
+            return x, ln[3], ln
+        return self.fwd(ctx, x) + (None,)
 
     def bwd(self, ctx: Ctx, x, dy, stats, accum=None):
         out = ctx.new(*x.shape)
@@ -479,17 +499,14 @@ class AttnE:
     def ln_fusable(self, ctx: Ctx, M: int) -> bool:
         """Can the LayerNorm in front of this attention be the prologue of the product that reads it (q | k | v of a
         self-attention, to_q of a cross-attention)?"""
-        # "live": the normalised tensor is an operand of something else too -- t = LN(x) A^T of an unmerged LoRA, or the
-        # weight gradient of a dense weight that trains (pre-training / ft_with_lora = False)
-        live = lambda L: (bool(L.r) and not (L.Wm is not None and not ctx.record)) or (ctx.record and L.tW is not None)
         if self.is_self:
             if self.fused_qkv is not None:
-                return ln_prologue_ok(ctx, M, 3 * self.inner, self.fused_qkv.K, live(self.fused_qkv))
+                return ln_prologue_ok(ctx, M, 3 * self.inner, self.fused_qkv.K, input_live(ctx, self.fused_qkv))
             if self.group is not None:
                 return ln_prologue_ok(ctx, M, 3 * self.inner, self.group.K, not (self.group.Wm is not None and not ctx.record)
                                       or any(ctx.record and L.tW is not None for L in self.group.members))
             return False          # three separate products would each normalise the rows again
-        return ln_prologue_ok(ctx, M, self.inner, self.q.K, live(self.q))
+        return ln_prologue_ok(ctx, M, self.inner, self.q.K, input_live(ctx, self.q))
 
     def _group_bwd(self, ctx: Ctx, dy, need_dx: bool, accum=None):
         """dy [M, G N] -> (dx [M, K] (+ accum) or None, u [M, G r])."""
@@ -525,7 +542,10 @@ class AttnE:
         (only where ln_fusable() said so).  ip = (k_ip, v_ip, Nip): image-prompt K / V of an IPCrossAttention, used when
         ip_live(); softmax over the text keys + ip_scale * softmax over the image-prompt keys in one launch."""
         if ip is not None and self.ip_live():
-            return self._fwd_ip(ctx, xn, c, B, N, Nkv, residual, kv_cache, ln, ip)
+            assert not self.is_self and not ctx.record, "the image-prompt attention is inference only"
+            ip = ip + (self.ip_scale,)
+        else:
+            ip = None
         inner, H = self.inner, self.heads
         tq = tk = tv = None
         pre = self._prescaled(ctx)
@@ -553,38 +573,10 @@ class AttnE:
                 k, v, tk, tv = self.project_context(ctx, c)
         a = ctx.new(B * N, inner)
         lse = torch.empty((B, H, rup(N, 64)), dtype=torch.float32, device=ctx.device) if ctx.record else None
-        if ctx.dtype == torch.bfloat16:       # transpose-free kernels (LDS transpose reads)
-            hip.attention_fwd_v2(q, k, v, a, lse, B, H, N, Nkv, self.dh, self.scale, q_prescaled=pre)
-        else:
-            kpad = rup(Nkv, 64)
-            vt = torch.empty((B, inner, kpad), dtype=ctx.dtype, device=ctx.device)
-            hip.transpose(v, vt, B, Nkv, inner, kpad, ldi=v.stride(0))
-            hip.attention_fwd(q, k, vt, a, lse, B, H, N, Nkv, self.dh, self.scale)
-            del vt
+        hip.attention(q, k, v, a, lse, B, H, N, Nkv, self.dh, self.scale, q_prescaled=pre, ip=ip)
         out, to_ = linear_fwd(ctx, self.o, a, residual=residual)
         saved = (xn, c, q, k, v, a, lse, tq, tk, tv, to_) if ctx.record else None
         return out, saved
-
-    def _fwd_ip(self, ctx: Ctx, xn, c, B, N, Nkv, residual, kv_cache, ln, ip):
-        assert not self.is_self and not ctx.record, "the image-prompt attention is inference only"
-        inner, H = self.inner, self.heads
-        pre = self._prescaled(ctx)
-        q, _ = linear_fwd(ctx, self.q, xn, alpha=self.q_alpha if pre else 1.0, ln=ln)
-        k, v = (kv_cache if kv_cache is not None else self.project_context(ctx, c))[:2]
-        k_ip, v_ip, Nip = ip
-        a = ctx.new(B * N, inner)
-        if ctx.dtype == torch.bfloat16:
-            hip.attention_fwd_ip(q, k, v, k_ip, v_ip, a, B, H, N, Nkv, Nip, self.dh, self.scale, self.ip_scale,
-                                 q_prescaled=pre)
-        else:
-            vt = torch.empty((B, inner, rup(Nkv, 64)), dtype=ctx.dtype, device=ctx.device)
-            hip.transpose(v, vt, B, Nkv, inner, vt.shape[-1], ldi=v.stride(0))
-            vt_ip = torch.empty((B, inner, 64), dtype=ctx.dtype, device=ctx.device)
-            hip.transpose(v_ip, vt_ip, B, Nip, inner, 64, ldi=v_ip.stride(0))
-            hip.attention_fwd_ip(q, k, vt, k_ip, vt_ip, a, B, H, N, Nkv, Nip, self.dh, self.scale, self.ip_scale)
-            del vt, vt_ip
-        out, _ = linear_fwd(ctx, self.o, a, residual=residual)
-        return out, None
 
     def bwd(self, ctx: Ctx, dout, saved, B, N, Nkv, accum_xn=None):
         """dout: gradient of the block output (residual path handled by the caller).
@@ -609,22 +601,8 @@ class AttnE:
             else:
                 dk = ctx.new(B * Nkv, inner) if want_kv else None
                 dv = ctx.new(B * Nkv, inner) if want_kv else None
-        if ctx.dtype == torch.bfloat16:
-            pre = self._prescaled(ctx)
-            # (-lse, -delta) of every query row as bf16 triples: lets the d_head-40 kernels fold them into their products
-            row_ws = torch.empty(lse.numel() * 8, dtype=torch.float32, device=ctx.device) if (pre and self.dh == 40) else None
-            hip.attention_bwd_v2(q, k, v, a, da, lse, delta, dq, dk, dv, B, H, N, Nkv, self.dh, self.scale,
-                                 q_prescaled=pre, row_ws=row_ws)
-        else:
-            npad, kpad = rup(N, 64), rup(Nkv, 64)
-            qt = torch.empty((B, inner, npad), dtype=ctx.dtype, device=ctx.device)
-            dot = torch.empty((B, inner, npad), dtype=ctx.dtype, device=ctx.device)
-            kt = torch.empty((B, inner, kpad), dtype=ctx.dtype, device=ctx.device)
-            hip.transpose(q, qt, B, N, inner, npad, ldi=q.stride(0))
-            hip.transpose(da, dot, B, N, inner, npad, ldi=da.stride(0))
-            hip.transpose(k, kt, B, Nkv, inner, kpad, ldi=k.stride(0))
-            hip.attention_bwd(q, k, v, a, da, qt, dot, kt, lse, delta, dq, dk, dv, B, H, N, Nkv, self.dh, self.scale)
-            del qt, dot, kt
+        hip.attention_backward(q, k, v, a, da, lse, delta, dq, dk, dv, B, H, N, Nkv, self.dh, self.scale,
+                               q_prescaled=self._prescaled(ctx))
         if self.is_self:
             if self.fused_qkv is not None:
                 dxn, _ = linear_bwd_data(ctx, self.fused_qkv, dqkv, accum=accum_xn)
@@ -687,31 +665,16 @@ class SpatialTransformerE:
         # needs the normalised tensor (ln_prologue_ok): then n_i below is the un-normalised input and s_i the statistics the
         # product wrote for the backward pass
         M = B * N
-        if self.attn1.ln_fusable(ctx, M):
-            l1 = self.ln1.prologue(ctx, M)
-            n1, s1 = h0, l1[3]
-        else:
-            l1 = None
-            n1, s1 = self.ln1.fwd(ctx, h0)
+        n1, s1, l1 = self.ln1.feed(ctx, h0, self.attn1.ln_fusable(ctx, M))
         h1, sv1 = self.attn1.fwd(ctx, n1, None, B, N, N, residual=h0, ln=l1)
-        if self.attn2.ln_fusable(ctx, M):
-            l2 = self.ln2.prologue(ctx, M)
-            n2, s2 = h1, l2[3]
-        else:
-            l2 = None
-            n2, s2 = self.ln2.fwd(ctx, h1)
+        n2, s2, l2 = self.ln2.feed(ctx, h1, self.attn2.ln_fusable(ctx, M))
         h2, sv2 = self.attn2.fwd(ctx, n2, c, B, N, Nkv, residual=h1, kv_cache=kv_cache, ln=l2, ip=ip)
         L = self.ff_proj
-        ff_live = (bool(L.r) and not (L.Wm is not None and not ctx.record)) or (ctx.record and L.tW is not None)
         xs_geglu = (not ctx.record and ctx.dtype == torch.bfloat16 and L.N % 64 == 0
                     and hip.xs_geglu_ok(M, L.K, 0 if L.Wm is not None else L.r))
         tile_geglu = not xs_geglu and not ctx.record and L.geglu_ok()
-        if not tile_geglu and ln_prologue_ok(ctx, M, L.N, L.K, ff_live, hip.ACT_GEGLU_SPLIT if xs_geglu else hip.ACT_NONE):
-            l3 = self.ln3.prologue(ctx, M)
-            n3, s3 = h2, l3[3]
-        else:
-            l3 = None
-            n3, s3 = self.ln3.fwd(ctx, h2)
+        n3, s3, l3 = self.ln3.feed(ctx, h2, not tile_geglu and ln_prologue_ok(
+            ctx, M, L.N, L.K, input_live(ctx, L), hip.ACT_GEGLU_SPLIT if xs_geglu else hip.ACT_NONE))
         if xs_geglu:
             # the same fusion on the x-stationary kernel (csrc/gemm_xs.hip): W's rows in their natural [value | gate] order
             tp = None

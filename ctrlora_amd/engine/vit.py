@@ -166,7 +166,7 @@ class ClipVisionE:
             b = dict(rows=new(B * (T - 1), self.Kpad), pe=new(B * (T - 1), D), h=[new(B * T, D) for _ in range(3)], x=new(B * T, D),
                      qkv=new(B * T, 3 * D), a=new(B * T, D), m=new(B * T, F), pooled=new(B, D),
                      embeds=new(B, self.cfg["projection_dim"], torch.float32))
-            if self.dtype == torch.float32:       # cl_attention_fwd reads V transposed, zero padded to whole 64-key tiles
+            if self.dtype == torch.float32:       # the fp32 kernels' V^T scratch at a fixed address (hip.attention checks its shape)
                 b["vt"] = torch.empty((B, D, rup(T, 64)), dtype=self.dtype, device=self.device)
             self._buf[B] = b
         return b
@@ -194,12 +194,7 @@ class ClipVisionE:
             hip.layernorm_fwd(hA, x, lay["ln1_g"], lay["ln1_b"], self.eps)
             hip.gemm(x, lay["qkv_w"], qkv, bias=lay["qkv_b"], alpha=qa, alpha_n=D if self.prescaled else 0)
             q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-            if self.dtype == torch.bfloat16:
-                hip.attention_fwd_v2(q, k, v, a, None, B, H, T, T, self.dh, self.scale, q_prescaled=self.prescaled)
-            else:
-                vt = b["vt"]
-                hip.transpose(v, vt, B, T, D, vt.shape[-1], ldi=v.stride(0))
-                hip.attention_fwd(q, k, vt, a, None, B, H, T, T, self.dh, self.scale)
+            hip.attention(q, k, v, a, None, B, H, T, T, self.dh, self.scale, q_prescaled=self.prescaled, vt=b.get("vt"))
             hip.gemm(a, lay["o_w"], hB, bias=lay["o_b"], residual=hA, beta=1.0)
             hip.layernorm_fwd(hB, x, lay["ln2_g"], lay["ln2_b"], self.eps)
             hip.gemm(x, lay["fc1_w"], m, bias=lay["fc1_b"], act=hip.ACT_GELU)

@@ -487,6 +487,53 @@ def attention_bwd_v2(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, N, Nkv, dh, s
                                    ATTN_Q_PRESCALED if q_prescaled else 0, ptr(row_ws), stream()), "cl_attention_bwd_v2")
 
 
+# The two kernel families behind one forward and one backward.  Which one runs is a function of the dtype alone: bf16 takes the
+# transpose-free kernels (_v2, the bf16 _ip), fp32 -- the parity mode -- the kernels that read materialised transposes
+# [B, H*dh, rows padded with zeros to whole 64-wide tiles].  The engine calls these two and never builds such a scratch itself.
+
+def _transposed(x, B, rows, inner, pad, out=None):
+    """x [B*rows, >=inner] row-major -> [B, inner, pad] zero padded (scratch of the call unless the caller passes `out`)."""
+    if out is None:
+        out = torch.empty((B, inner, pad), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (B, inner, pad) and out.dtype == x.dtype
+    return transpose(x, out, B, rows, inner, pad, ldi=x.stride(0))
+
+
+def attention(q, k, v, o, lse, B, H, N, Nkv, dh, scale, *, q_prescaled=False, ip=None, vt=None):
+    """o = softmax(scale q k^T) v per head; q [B*N, >=H*dh], k and v [B*Nkv, >=H*dh] row-major, lse [B, H, stride] or None.
+    ip = (k_ip, v_ip, Nip, ip_scale), v_ip row-major like k_ip: + ip_scale * softmax(scale q k_ip^T) v_ip in the same launch
+    (attention_fwd_ip; forward only).  vt: the fp32 family's V^T scratch [B, H*dh, rup(Nkv, 64)] for a caller that replays
+    fixed addresses; allocated here, and released on return, otherwise."""
+    assert ip is None or lse is None
+    if dt(q) == BF16:
+        if ip is None:
+            return attention_fwd_v2(q, k, v, o, lse, B, H, N, Nkv, dh, scale, q_prescaled=q_prescaled)
+        k_ip, v_ip, Nip, ip_scale = ip
+        return attention_fwd_ip(q, k, v, k_ip, v_ip, o, B, H, N, Nkv, Nip, dh, scale, ip_scale, q_prescaled=q_prescaled)
+    assert not q_prescaled, "the fp32 kernels scale the scores themselves"
+    vt = _transposed(v, B, Nkv, H * dh, (Nkv + 63) // 64 * 64, vt)
+    if ip is None:
+        return attention_fwd(q, k, vt, o, lse, B, H, N, Nkv, dh, scale)
+    k_ip, v_ip, Nip, ip_scale = ip
+    vt_ip = _transposed(v_ip, B, Nip, H * dh, 64)          # Nip <= 64: one masked tile
+    return attention_fwd_ip(q, k, vt, k_ip, vt_ip, o, B, H, N, Nkv, Nip, dh, scale, ip_scale)
+
+
+def attention_backward(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, N, Nkv, dh, scale, *, q_prescaled=False):
+    """dq, dk, dv (dk / dv may be None) of attention(); lse as the forward wrote it, delta a scratch of lse's shape."""
+    if dt(q) == BF16:
+        # (-lse, -delta) of every query row as bf16 triples: lets the d_head-40 kernels fold them into their products
+        row_ws = torch.empty(lse.numel() * 8, dtype=torch.float32, device=q.device) if (q_prescaled and dh == 40) else None
+        return attention_bwd_v2(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, N, Nkv, dh, scale, q_prescaled=q_prescaled,
+                                row_ws=row_ws)
+    assert not q_prescaled, "the fp32 kernels scale the scores themselves"
+    inner, npad, kpad = H * dh, (N + 63) // 64 * 64, (Nkv + 63) // 64 * 64
+    qt = _transposed(q, B, N, inner, npad)
+    dot = _transposed(do, B, N, inner, npad)
+    kt = _transposed(k, B, Nkv, inner, kpad)
+    attention_bwd(q, k, v, o, do, qt, dot, kt, lse, delta, dq, dk, dv, B, H, N, Nkv, dh, scale)
+
+
 # ------------------------------------------------------------------ elementwise / layout
 
 def geglu_fwd(h, out):
