@@ -306,5 +306,9 @@ int cl_tick(int* counter, void* stream) { return tick(counter, S(stream)); }
 int cl_adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, void* stream) { return adamw_dev(p, g, m, v, n, hyper, step, S(stream)); }
 int cl_ddim_set_t(const long* table, const int* cursor, int S_, long* ts, int n, void* stream) { return ddim_set_t(table, cursor, S_, ts, n, S(stream)); }
 int cl_ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef, const int* cursor, int S_, float scale, float* x_prev, float* pred_x0, long n, void* stream) { return ddim_step_dev(x, e_c, e_u, noise, coef, cursor, S_, scale, x_prev, pred_x0, n, S(stream)); }
+int cl_timestep_embedding_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, void* stream) { return timestep_embed_f(dtype, t, freqs, out, ldo, B, half, S(stream)); }
+int cl_dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S_, float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream) { return dpmpp_step(x, e_c, e_u, coef, index, S_, scale, hist, x_next, pred_x0, n, S(stream)); }
+int cl_dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S_, float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream) { return dpmpp_step_dev(x, e_c, e_u, coef, cursor, S_, scale, hist, x_next, pred_x0, n, S(stream)); }
+int cl_dpm_set_t(const float* coef, const int* cursor, int S_, float* ts, int n, void* stream) { return dpm_set_t(coef, cursor, S_, ts, n, S(stream)); }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ int transpose(int in_dtype, int out_dtype, const void* in, long ldi, long bsi, v
 int nchw_to_tok(int dtype, const float* in, void* out, long ldo, int B, int Cin, int Cpad, int HW, hipStream_t st);
 int tok_to_nchw(int dtype, const void* in, long ldi, float* out, int B, int C, int HW, float alpha, float beta, hipStream_t st);
 int timestep_embed(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st);
+int timestep_embed_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st);
 int qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
             float* out, int B, long per, hipStream_t st);
 int mse_loss(const float* eps, const float* target, float* d_eps, float* loss, long n, float gscale, hipStream_t st);
@@ -31,6 +32,12 @@ int adamw_dev(float* p, const float* g, float* m, float* v, long n, const float*
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st);
 int ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                   const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, hipStream_t st);
+// DPM-Solver++ multistep update over a [S][8] coefficient table and a [3][n] ring of x0 predictions (elementwise.hip)
+int dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S, float scale,
+               float* hist, float* x_next, float* pred_x0, long n, hipStream_t st);
+int dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                   float scale, float* hist, float* x_next, float* pred_x0, long n, hipStream_t st);
+int dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, hipStream_t st);
 int adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
           float wd, int step, float gscale, hipStream_t st);
 int pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, hipStream_t st);

@@ -170,6 +170,19 @@ __global__ void timestep_embed_kernel(const long* __restrict__ t, const float* _
   out[(long)b * ldo + half + k] = from_f<T>(sinf(arg));
 }
 
+// timestep_embedding at a FLOATING-POINT time (the DPM-Solver++ time grid is not integer: 949.05, 899.1, ...): the
+// argument is t[b] * freqs[k] in fp32, so an integer-valued t gives the bits of timestep_embed_kernel
+template <typename T>
+__global__ void timestep_embed_f_kernel(const float* __restrict__ t, const float* __restrict__ freqs,
+                                        T* __restrict__ out, long ldo, int B, int half) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * half) return;
+  const int b = i / half, k = i - b * half;
+  const float arg = t[b] * freqs[k];
+  out[(long)b * ldo + k] = from_f<T>(cosf(arg));
+  out[(long)b * ldo + half + k] = from_f<T>(sinf(arg));
+}
+
 // ---------------------------------------------------------------- q_sample + MSE (ddpm.py:356-359,902)
 // x_noisy = sqrt_ac[t_b] * z + sqrt_1mac[t_b] * noise       (fp32, any layout; per = elems per sample)
 __global__ void qsample_kernel(const float* __restrict__ z, const float* __restrict__ noise,
@@ -395,6 +408,55 @@ __global__ void ddim_step_dev_kernel(const float* __restrict__ x, const float* _
     x_prev[i] = xp;            // x_prev may alias x (element-wise)
     if (pred_x0) pred_x0[i] = p0;
   }
+}
+
+// ---------------------------------------------------------------- DPM-Solver++ multistep update (data prediction)
+// coef = device table [S][8] fp32, row i = {alpha_i, sigma_i, cx_i, c0_i, c1_i, c2_i, t_in_i, 0}; hist = [3][n] fp32 ring,
+// model value k lives in slot k % 3.  Step i:  e = guided eps;  m = (x - sigma_i e) / alpha_i;  hist[i % 3] = m;
+//   x_next = cx_i x + c0_i m + c1_i hist[(i + 2) % 3] + c2_i hist[(i + 1) % 3]
+// A term whose coefficient is exactly 0 is not read (the start-up steps would read uninitialised slots).  x_next may
+// alias x (element-wise), so neither is __restrict__.  One body for the host-index and the device-cursor launch: an
+// eager and a replayed step give the same bits.
+__device__ __forceinline__ void dpmpp_step_body(const float* x, const float* __restrict__ e_c,
+                                                const float* __restrict__ e_u, const float* __restrict__ coef,
+                                                int index, float scale, float* hist, float* x_next,
+                                                float* __restrict__ pred_x0, long n) {
+  const float* row = coef + (long)index * 8;
+  const float alpha = row[0], sigma = row[1], cx = row[2], c0 = row[3], c1 = row[4], c2 = row[5];
+  float* h0 = hist + (long)(index % 3) * n;
+  const float* h1 = hist + (long)((index + 2) % 3) * n;
+  const float* h2 = hist + (long)((index + 1) % 3) * n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float e = e_c[i];
+    if (e_u) { const float u = e_u[i]; e = u + scale * (e - u); }
+    const float xi = x[i];
+    const float m = (xi - sigma * e) / alpha;
+    float xn = cx * xi + c0 * m;
+    if (c1 != 0.0f) xn += c1 * h1[i];
+    if (c2 != 0.0f) xn += c2 * h2[i];
+    h0[i] = m;
+    x_next[i] = xn;
+    if (pred_x0) pred_x0[i] = m;
+  }
+}
+__global__ void dpmpp_step_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                  const float* __restrict__ coef, int index, float scale, float* hist, float* x_next,
+                                  float* __restrict__ pred_x0, long n) {
+  dpmpp_step_body(x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0, n);
+}
+// device cursor i = 0..S-1 = the table row (clamped, so a replay past the end cannot index outside the table)
+__global__ void dpmpp_step_dev_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                      const float* __restrict__ coef, const int* __restrict__ cursor, int S, float scale,
+                                      float* hist, float* x_next, float* __restrict__ pred_x0, long n) {
+  const int index = min(max(*cursor, 0), S - 1);
+  dpmpp_step_body(x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0, n);
+}
+// ts[:] = t_in of row min(cursor, S - 1): the (float) model time of the step the cursor points at
+__global__ void dpm_set_t_kernel(const float* __restrict__ coef, const int* __restrict__ cursor, int S,
+                                 float* __restrict__ ts, int n) {
+  const int index = min(max(*cursor, 0), S - 1);
+  const float t = coef[(long)index * 8 + 6];
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) ts[i] = t;
 }
 
 // ---------------------------------------------------------------- 2x2 sum pool (data-gradient of nearest x2)
@@ -649,6 +711,13 @@ int timestep_embed(int dtype, const long* t, const float* freqs, void* out, long
   else hipLaunchKernelGGL((timestep_embed_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
   CL_CHECK_LAUNCH(); return CL_OK;
 }
+int timestep_embed_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st) {
+  const int n = B * half;
+  if (n < 1) return CL_EINVAL;
+  if (dtype == CL_BF16) hipLaunchKernelGGL((timestep_embed_f_kernel<bf16_t>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (bf16_t*)out, ldo, B, half);
+  else hipLaunchKernelGGL((timestep_embed_f_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
 int qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
             float* out, int B, long per, hipStream_t st) {
   hipLaunchKernelGGL(qsample_kernel, dim3(ew_grid(B * per)), dim3(256), 0, st, z, noise, t, sqrt_ac, sqrt_1mac, out, per, (long)B * per);
@@ -730,6 +799,23 @@ int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hip
 int ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                   const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, hipStream_t st) {
   hipLaunchKernelGGL(ddim_step_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, noise, coef, cursor, S, scale, x_prev, pred_x0, n);
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
+int dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S, float scale,
+               float* hist, float* x_next, float* pred_x0, long n, hipStream_t st) {
+  if (S < 1 || index < 0 || index >= S || n < 1) return CL_EINVAL;
+  hipLaunchKernelGGL(dpmpp_step_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0, n);
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
+int dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                   float scale, float* hist, float* x_next, float* pred_x0, long n, hipStream_t st) {
+  if (S < 1 || n < 1) return CL_EINVAL;
+  hipLaunchKernelGGL(dpmpp_step_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, coef, cursor, S, scale, hist, x_next, pred_x0, n);
+  CL_CHECK_LAUNCH(); return CL_OK;
+}
+int dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, hipStream_t st) {
+  if (S < 1 || n < 1) return CL_EINVAL;
+  hipLaunchKernelGGL(dpm_set_t_kernel, dim3(1), dim3(256), 0, st, coef, cursor, S, ts, n);
   CL_CHECK_LAUNCH(); return CL_OK;
 }
 int pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, hipStream_t st) {

@@ -59,7 +59,7 @@ class CtrLoRAEngine:
         IPCrossAttention layers (cldm/cldm_style.py), or None."""
         B, _, H, W = x_noisy.shape
         ctx = Ctx(self.dtype, self.device, False)
-        t = t.to(device=self.device, dtype=torch.long).contiguous()
+        t = self._time_in(t)
         c = self._ctx_in(context)
         cip = self._ip_in(context_ip, B)
         semb, hs, dims, h_mid = self.unet.encode(ctx, self._tok_in(x_noisy), t, c, B, H, W, c_ip=cip)
@@ -79,6 +79,12 @@ class CtrLoRAEngine:
         return hip.tok_to_nchw(eps_tok, eps)
 
     # ---------------------------------------------------------------- boundary conversions
+    def _time_in(self, t: torch.Tensor) -> torch.Tensor:
+        """Timesteps as the embedding kernels take them: an integer t as int64 (cl_timestep_embedding), a floating-point t
+        -- a solver's non-integer model time -- as fp32 (cl_timestep_embedding_f), never truncated."""
+        dtype = torch.float32 if t.is_floating_point() else torch.long
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
     def _tok_in(self, x_nchw: torch.Tensor) -> torch.Tensor:
         B, C, H, W = x_nchw.shape
         out = torch.empty((B * H * W, rup(C, 32)), dtype=self.dtype, device=self.device)
@@ -108,12 +114,13 @@ class CtrLoRAEngine:
     @torch.no_grad()
     def forward(self, x_noisy, t, context, hints: Optional[Sequence[torch.Tensor]], control_scales=None,
                 lora_weights=None, record: bool = False, only_mid_control: bool = False, context_ip=None) -> torch.Tensor:
-        """x_noisy (B,4,H,W) fp32, t (B,) int64, context (B,L,D), hints: one latent (B,4,H,W) per
+        """x_noisy (B,4,H,W) fp32, t (B,) int64 (or floating point: a solver's non-integer time), context (B,L,D), hints: one latent (B,4,H,W) per
         ControlNet bank or None (plain UNet).  context_ip (B,Nip,D): image-prompt tokens for the UNet's
         IPCrossAttention layers (inference only; the ControlNets never see them).  Returns eps (B,out_channels,H,W) fp32."""
         B, _, H, W = x_noisy.shape
         ctx = Ctx(self.dtype, self.device, record)
-        t = t.to(device=self.device, dtype=torch.long).contiguous()
+        t = self._time_in(t)
+        assert not (record and t.is_floating_point()), "training steps take integer timesteps"
         c = self._ctx_in(context)
         cip = self._ip_in(context_ip, B)
         assert cip is None or not record, "the image-prompt attention is inference only"
@@ -185,7 +192,7 @@ class CtrLoRAEngine:
         B, _, H, W = hint.shape
         ctx = Ctx(self.dtype, self.device, False)
         cn = self.controls[bank]
-        t = t.to(device=self.device, dtype=torch.long).contiguous()
+        t = self._time_in(t)
         c = self._ctx_in(context)
         # output grids: follow the encoder's down-sampling
         dims, hh, ww = [], H, W

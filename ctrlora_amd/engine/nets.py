@@ -350,7 +350,10 @@ class _TimeEmbed:
     def fwd(self, ctx: Ctx, t: torch.Tensor):
         B = t.shape[0]
         temb = ctx.new(B, self.mc)
-        hip.timestep_embedding(t, self.freqs, temb)
+        if t.dtype == torch.float32:        # a sampler's non-integer time (DPM-Solver++); integer t: the long kernel as before
+            hip.timestep_embedding_f(t, self.freqs, temb)
+        else:
+            hip.timestep_embedding(t, self.freqs, temb)
         te0, t0 = linear_fwd(ctx, self.l0, temb)
         h = ctx.new(B, self.ted); hip.silu_fwd(te0, h)
         emb, t2 = linear_fwd(ctx, self.l2, h)

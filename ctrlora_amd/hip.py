@@ -115,6 +115,10 @@ _SIGS = {
     "cl_ddim_set_t": [_P, _P, _I, _P, _I, _P],
     "cl_ddim_step_dev": [_P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _L, _P],
     "cl_adamw": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
+    "cl_timestep_embedding_f": [_I, _P, _P, _P, _L, _I, _I, _P],
+    "cl_dpmpp_step": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _L, _P],
+    "cl_dpmpp_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
+    "cl_dpm_set_t": [_P, _P, _I, _P, _I, _P],
 }
 EXPORTED = tuple(_SIGS.keys())
 # probe hooks (ctrlora_amd/csrc/debug_hooks.h): exported by the library, not part of include/ctrlora_hip.h
@@ -633,6 +637,14 @@ def timestep_embedding(t_long, freqs, out):
     return out
 
 
+def timestep_embedding_f(t_f32, freqs, out):
+    """timestep_embedding at floating-point times (t fp32, contiguous): cl_timestep_embedding_f."""
+    assert t_f32.dtype == torch.float32 and t_f32.is_contiguous()
+    _chk(lib().cl_timestep_embedding_f(dt(out), t_f32.data_ptr(), freqs.data_ptr(), out.data_ptr(), ld(out),
+                                       t_f32.shape[0], freqs.shape[0], stream()), "cl_timestep_embedding_f")
+    return out
+
+
 def qsample(z, noise, t, sqrt_ac, sqrt_1mac, out):
     B = z.shape[0]
     _chk(lib().cl_qsample(z.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
@@ -709,3 +721,36 @@ def ddim_step_dev(x, e_c, e_u, noise, coef, cursor, S, scale, x_prev, pred_x0=No
     _chk(lib().cl_ddim_step_dev(x.data_ptr(), e_c.data_ptr(), ptr(e_u), ptr(noise), coef.data_ptr(), cursor.data_ptr(),
                                 S, scale, x_prev.data_ptr(), ptr(pred_x0), x.numel(), stream()), "cl_ddim_step_dev")
     return x_prev
+
+
+def _dpm_args(x, e_c, e_u, coef, S, hist, x_next, pred_x0):
+    n = x.numel()
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (S, 8), tuple(coef.shape)
+    assert hist.dtype == torch.float32 and hist.is_contiguous() and hist.numel() == 3 * n
+    for t in (x, e_c, e_u, x_next, pred_x0):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    return n
+
+
+def dpmpp_step(x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0=None):
+    """One DPM-Solver++ multistep update on row `index` of the [S][8] table (cl_dpmpp_step); x_next may be x."""
+    S = coef.shape[0]
+    n = _dpm_args(x, e_c, e_u, coef, S, hist, x_next, pred_x0)
+    _chk(lib().cl_dpmpp_step(x.data_ptr(), e_c.data_ptr(), ptr(e_u), coef.data_ptr(), index, S, scale, hist.data_ptr(),
+                             x_next.data_ptr(), ptr(pred_x0), n, stream()), "cl_dpmpp_step")
+    return x_next
+
+
+def dpmpp_step_dev(x, e_c, e_u, coef, cursor, S, scale, hist, x_next, pred_x0=None):
+    """dpmpp_step with the row taken from a device cursor (hipGraph-replayable): cl_dpmpp_step_dev."""
+    n = _dpm_args(x, e_c, e_u, coef, S, hist, x_next, pred_x0)
+    _chk(lib().cl_dpmpp_step_dev(x.data_ptr(), e_c.data_ptr(), ptr(e_u), coef.data_ptr(), cursor.data_ptr(), S, scale,
+                                 hist.data_ptr(), x_next.data_ptr(), ptr(pred_x0), n, stream()), "cl_dpmpp_step_dev")
+    return x_next
+
+
+def dpm_set_t(coef, cursor, S, ts):
+    """ts[:] = the model input time (fp32) of row min(cursor, S - 1) of the DPM-Solver++ table: cl_dpm_set_t."""
+    assert ts.dtype == torch.float32 and ts.is_contiguous() and tuple(coef.shape) == (S, 8)
+    _chk(lib().cl_dpm_set_t(coef.data_ptr(), cursor.data_ptr(), S, ts.data_ptr(), ts.numel(), stream()), "cl_dpm_set_t")
+    return ts

@@ -320,6 +320,10 @@ int cl_repack(int dtype, const float* flat, const long* desc, const int* tile_pr
               int total_tiles, void* stream);
 /* timestep_embedding (util.py:154-174); freqs = the fp32 table exp(-ln(1e4) * arange(half)/half) */
 int cl_timestep_embedding(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, void* stream);
+/* The same embedding at floating-point times (added in ABI 7, compatible): the argument is t[b] * freqs[j] in fp32, cos | sin
+ * rounded once into `dtype`; an integer-valued t gives the bits of cl_timestep_embedding.  The DPM-Solver++ time grid
+ * (ldm/models/diffusion/dpm_solver) is not integer: 999, 949.05, 899.1, ... for 20 steps. */
+int cl_timestep_embedding_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, void* stream);
 
 /* out[m, :] = x[pixel(m, tap), :] (zero outside the image), m = (b, oy, ox), pixel = (oy*stride + tap/3 - pad,
  * ox*stride + tap%3 - pad): the shifted operand of one tap of a 3x3 conv weight gradient, materialised (fp32 parity
@@ -366,6 +370,23 @@ int cl_adamw_dev(float* p, const float* g, float* m, float* v, long n, const flo
 int cl_ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, void* stream);
 int cl_ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                      const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, void* stream);
+
+/* ---- DPM-Solver++ (multistep, data prediction), added in ABI 7 (compatible) ----------------
+ * One sampler step after the model evaluation, as one launch.  coef = device [S][8] fp32 table, row i =
+ * {alpha_i, sigma_i, cx_i, c0_i, c1_i, c2_i, t_in_i, 0}; hist = device [3][n] fp32 ring of x0 predictions, model value k in
+ * slot k % 3.  Step i:
+ *   e = e_u ? e_u + scale (e_c - e_u) : e_c          m = (x - sigma_i e) / alpha_i          hist[i % 3] = m
+ *   x_next = cx_i x + c0_i m + c1_i hist[(i + 2) % 3] + c2_i hist[(i + 1) % 3]
+ * A term whose coefficient is exactly 0 is not read (those slots are uninitialised in the first steps).  x_next may alias x;
+ * pred_x0 may be NULL and receives m.  cl_dpmpp_step takes the row from the host and returns 1 for S < 1 or an index outside
+ * [0, S); cl_dpmpp_step_dev takes it from a device cursor (clamped to [0, S - 1]) so that the step replays as a hipGraph; both
+ * run the same device code and give the same bits.  cl_dpm_set_t: ts[0 .. n) = coef[min(cursor, S - 1)][6], the model's
+ * (float) input time of the step the cursor points at.  The caller advances the cursor with cl_tick. */
+int cl_dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S, float scale,
+                  float* hist, float* x_next, float* pred_x0, long n, void* stream);
+int cl_dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                      float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream);
+int cl_dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,9 @@ def get_parser():
     p.add_argument("--strength", type=float, default=1.0, help="strength of controlnet")
     p.add_argument("--cfg", type=float, default=7.5, help="unconditional guidance scale")
     p.add_argument("--empty_prompt", action="store_true", default=False, help="experimental: use empty prompt")
+    p.add_argument("--sampler", type=str, choices=["ddim", "dpm"], default="ddim",
+                   help="ddim (the reference script's sampler) or dpm: DPM-Solver++ (multistep, order 2), which takes "
+                        "--ddim_steps as its number of steps (20 is usual) and ignores --ddim_eta")
     return p
 
 
@@ -82,10 +85,17 @@ def sample_dataset(model, sampler, dataset, args, device="cuda"):
     return n
 
 
+def make_sampler(model, name="ddim"):
+    if name == "dpm":
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        return DPMSolverSampler(model)
+    from cldm.ddim_hacked import DDIMSampler
+    return DDIMSampler(model)
+
+
 def main(argv=None):
     from torch.utils.data import Subset
     from cldm.cldm_ctrlora_pretrain import ControlPretrainLDM
-    from cldm.ddim_hacked import DDIMSampler
     from cldm.model import create_model, load_state_dict
     args = get_parser().parse_args(argv)
     if args.multigen20m:
@@ -108,7 +118,7 @@ def main(argv=None):
     model = model.cuda().eval()
     print(f"Successfully load model ckpt from {args.ckpt}")
     os.makedirs(args.save_dir, exist_ok=True)
-    sample_dataset(model, DDIMSampler(model), dataset, args)
+    sample_dataset(model, make_sampler(model, args.sampler), dataset, args)
     print("Done")
 
 

@@ -1,0 +1,87 @@
+"""DDIM with 50 steps against DPM-Solver++ with 20 at the benchmark's DDIM shape (B = 16, CFG 7.5, latent 64, SD1.5 width, bf16).
+
+    python tools/bench_sampler.py [--rounds 5] [--ddim-steps 50] [--dpm-steps 20] [--out FILE]
+
+Both legs sample from the same model with the same tensors through one sample() call each, as a one-shot user pays it:
+the first step eager, the second captured as a hipGraph, the rest replayed (neither leg keeps a graph across calls: the
+DPM-Solver++ sampler has no reuse_graph, so DDIM's stays off here and its figure is the "cold" one of bench.py, not the
+headline).  A call ends in a device synchronise and is timed with the host clock; both legs run once untimed at their
+timed length, then alternate round by round so that clock drift hits both; the medians are reported.  ms per step is
+ms per batch over the number of steps, so it carries each leg's share of the eager step and the capture.  One JSON line;
+a missing GPU is an error, not a fallback.  Whether 20 DPM-Solver++ steps match the quality of 50 DDIM steps is the
+solver paper's claim (arXiv:2211.01095), not something this tool measures.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--ddim-steps", type=int, default=50)
+    ap.add_argument("--dpm-steps", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--tiny", action="store_true", help="narrow model: a rehearsal of the tool, not a measurement")
+    ap.add_argument("--out", type=str, default=None, help="also write the JSON line to this file")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_sampler.py needs a GPU: a CPU timing says nothing about the samplers")
+    import bench
+    from cldm.ddim_hacked import DDIMSampler
+    from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+    B, H = a.batch, 64
+    model = bench.build_model("inference/ctrlora_sd15_rank128_1lora.yaml", 0, tiny=a.tiny).cuda().eval()
+    model.set_engine_dtype(torch.bfloat16)
+    cd = model.control_model.context_dim
+    g = torch.Generator().manual_seed(7)
+    hint = torch.randn(B, 4, H, H, generator=g).cuda()
+    cond = {"c_concat": [hint], "c_crossattn": [torch.randn(B, 77, cd, generator=g).cuda()]}
+    unc = {"c_concat": [hint], "c_crossattn": [torch.randn(B, 77, cd, generator=g).cuda()]}
+    x_T = torch.randn(B, 4, H, H, generator=g).cuda()
+    legs = {"ddim": (DDIMSampler(model), a.ddim_steps), "dpm": (DPMSolverSampler(model), a.dpm_steps)}
+
+    def run(name):
+        sampler, S = legs[name]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out, _ = sampler.sample(S, B, (4, H, H), cond, verbose=False, eta=0.0, x_T=x_T, unconditional_guidance_scale=7.5,
+                                unconditional_conditioning=unc)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert bool(torch.isfinite(out).all()), name
+        return dt
+
+    for name in legs:           # warm-up at the timed length: code objects, allocator, the capture path
+        run(name)
+    times = {name: [] for name in legs}
+    for _ in range(a.rounds):
+        for name in legs:
+            times[name].append(run(name))
+    res = dict(metric="ms per batch of one sample() call (eager first step + capture + replays), CFG 7.5, both passes batched",
+               batch=B, latent=H, dtype="bf16", rounds=a.rounds, tiny=bool(a.tiny), gpu=torch.cuda.get_device_name(0))
+    for name, (_, S) in legs.items():
+        ts = sorted(times[name])
+        med = ts[len(ts) // 2]
+        res[name] = dict(steps=S, ms_per_batch=round(med * 1e3, 2), ms_per_step=round(med / S * 1e3, 3),
+                         min_ms_per_batch=round(ts[0] * 1e3, 2), max_ms_per_batch=round(ts[-1] * 1e3, 2))
+    res["dpm_over_ddim_batch_time"] = round(res["dpm"]["ms_per_batch"] / res["ddim"]["ms_per_batch"], 4)
+    res["dpm_over_ddim_step_time"] = round(res["dpm"]["ms_per_step"] / res["ddim"]["ms_per_step"], 4)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
