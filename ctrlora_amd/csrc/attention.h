@@ -11,7 +11,7 @@ namespace cl {
 //   Vt : [B][inner][nkv_pad]  transposed V, zero padded to a multiple of 64 keys (forward)
 //   O  : [B*N,   ldo]
 //   LSE: [B][H][lse_stride] fp32, log2-domain log-sum-exp of scale*log2(e)*q.k (saved for
-//        backward); lse_stride = N rounded up to a multiple of 64
+//        backward); lse_stride = a multiple of 64, >= N (N rounded up, or more): forward and backward refuse anything else
 struct AttnFwdArgs {
   const void* Q; long ldq;
   const void* K; long ldk;
@@ -67,5 +67,27 @@ extern int g_attn_variant;   // probe hook: 0 = heuristic, 1 = tile-synchronous 
 bool attn_fwd40_applies(const AttnFwdArgs& a);
 int attn_fwd40(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st);
 int attn_delta(const AttnBwdArgs& a, hipStream_t st);   // delta[q] = sum_d dO[q,d] O[q,d]  (bf16)
+
+// Read-only record of what the last attention entry point launched (csrc/debug_hooks.h: cl_debug_attention_last_launch).
+// Host side only: every launcher of the four attention files fills it next to its hipLaunchKernelGGL; an entry point that
+// refuses its arguments leaves kind = 0.  No kernel, launch or argument depends on it.
+enum { ATTN_FAM_TR = 1, ATTN_FAM_TR_IP = 2, ATTN_FAM_HYB = 3, ATTN_FAM_FWD40 = 4, ATTN_FAM_FOLD = 5, ATTN_FAM_TRANSPOSED = 6 };
+enum { ATTN_BIT_TAIL = 1, ATTN_BIT_TQ = 2, ATTN_BIT_TK = 4, ATTN_BIT_PRIO = 8 };
+struct AttnLaunchRec {
+  int kind;          // 0 nothing launched, 1 forward, 2 backward
+  int family;        // ATTN_FAM_*
+  int dtype, dh;
+  int fwd_frags, dq_frags, dkv_frags;   // 64-row fragments per workgroup pass (0 = that kernel did not run)
+  int bits;          // ATTN_BIT_*: the TAIL / TQ / TK template forms, s_setprio form
+  int lookahead, remap;                 // hybrid / fwd40 forward
+  int delta_launch, dkv_ran;            // backward: separate delta kernel, dK/dV kernel
+  int grid_fwd, grid_dq, grid_dkv;      // workgroups
+  int tile;          // keys / queries per staged tile along the looped dimension
+};
+extern AttnLaunchRec g_attn_last;
+inline void attn_rec_begin() { g_attn_last = AttnLaunchRec{}; }
+inline void attn_rec(int kind, int family, int dtype, int dh) {
+  g_attn_last.kind = kind; g_attn_last.family = family; g_attn_last.dtype = dtype; g_attn_last.dh = dh; g_attn_last.tile = 64;
+}
 
 }  // namespace cl

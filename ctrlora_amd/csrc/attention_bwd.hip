@@ -306,9 +306,14 @@ static int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {
   if (a.dK) {
     dim3 grid((a.Nkv + 63) / 64, a.H, a.B);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DH, BT>), grid, dim3(256), LDS_DKV, st, a);
+    g_attn_last.dkv_ran = 1; g_attn_last.dkv_frags = 1; g_attn_last.grid_dkv = (int)(grid.x * grid.y * grid.z);
   }
   dim3 gridq((a.N + 63) / 64, a.H, a.B);
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DH, BT>), gridq, dim3(256), LDS_DQ, st, a);
+  attn_rec(2, ATTN_FAM_TRANSPOSED, EB == 2 ? CL_BF16 : CL_F32, DH);
+  g_attn_last.dq_frags = 1; g_attn_last.grid_dq = (int)(gridq.x * gridq.y * gridq.z);
+  g_attn_last.delta_launch = 1; g_attn_last.tile = BT;
+  g_attn_last.bits = (a.N % 64 ? ATTN_BIT_TQ : 0) | (a.Nkv % 64 ? ATTN_BIT_TK : 0);
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
@@ -336,6 +341,7 @@ int attn_delta(const AttnBwdArgs& a, hipStream_t st) {
 }
 
 int attn_bwd(const AttnBwdArgs& a, int dtype, hipStream_t st) {
+  attn_rec_begin();
   if (a.q_prescaled) return CL_EINVAL;   // the pre-scaled-Q contract is the transpose-free bf16 kernels' (attention_tr.hip)
   const int eb = dtype == CL_BF16 ? 2 : 4;
   if ((a.ldq * eb) % 16 || (a.ldk * eb) % 16 || (a.ldv * eb) % 16 || (a.lddo * eb) % 16 || (a.ldo * eb) % 16)

@@ -419,6 +419,8 @@ static int launch_fwd(const AttnFwdArgs& a, hipStream_t st) {
   }
   dim3 grid((a.N + 64 * QW - 1) / (64 * QW), a.H, a.B);
   hipLaunchKernelGGL((attn_fwd_kernel<T, DH, QW, BKV>), grid, dim3(256), LDS, st, a);
+  attn_rec(1, ATTN_FAM_TRANSPOSED, EB == 2 ? CL_BF16 : CL_F32, DH);
+  g_attn_last.fwd_frags = QW; g_attn_last.tile = BKV; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
@@ -463,11 +465,14 @@ static int launch_fwd_ip(const AttnFwdArgs& a, const AttnIpArgs& ip, hipStream_t
   }
   dim3 grid((a.N + 63) / 64, a.H, a.B);
   hipLaunchKernelGGL((attn_fwd_ip_kernel<float, DH, 1, BKV>), grid, dim3(256), LDS, st, a, ip);
+  attn_rec(1, ATTN_FAM_TR_IP, CL_F32, DH);
+  g_attn_last.fwd_frags = 1; g_attn_last.tile = BKV; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
 
 int attn_fwd_ip(const AttnFwdArgs& a, const AttnIpArgs& ip, int dtype, hipStream_t st) {
+  attn_rec_begin();
   if (dtype != CL_F32 || a.q_prescaled || a.LSE) return CL_EINVAL;
   if ((a.ldq * 4) % 16 || (a.ldk * 4) % 16 || a.nkv_pad % 64 || a.nkv_pad < a.Nkv || a.Nkv < 1 || a.N < 1) return CL_EINVAL;
   if ((a.ldo * 4) % 16 || (ip.ldk2 * 4) % 16 || ip.ldv2 % 64 || ip.ldv2 < ip.Nip || ip.Nip < 1 || ip.Nip > 64 || !ip.K2 || !ip.V2)
@@ -484,11 +489,13 @@ int attn_fwd_ip(const AttnFwdArgs& a, const AttnIpArgs& ip, int dtype, hipStream
 }
 
 int attn_fwd(const AttnFwdArgs& a, int dtype, hipStream_t st) {
+  attn_rec_begin();
   if (a.q_prescaled) return CL_EINVAL;   // the pre-scaled-Q contract is the transpose-free bf16 kernels' (attention_tr.hip)
   const int eb = dtype == CL_BF16 ? 2 : 4;
   if ((a.ldq * eb) % 16 || (a.ldk * eb) % 16 || a.nkv_pad % 64 || a.nkv_pad < a.Nkv || a.Nkv < 1 || a.N < 1)
     return CL_EINVAL;
   if ((a.ldo * eb) % 16) return CL_EINVAL;
+  if (a.LSE && (a.lse_stride % 64 || a.lse_stride < a.N)) return CL_EINVAL;   // as the backward: rows of neighbouring heads must not overlap
   return dtype == CL_BF16 ? dispatch_dh<bf16_t>(a, st) : dispatch_dh<float>(a, st);
 }
 

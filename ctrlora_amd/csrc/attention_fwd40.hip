@@ -459,6 +459,8 @@ int attn_fwd40(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st) {
   const long grid = (long)nqb * a.H * a.B;
   const int remap = ((a.B * a.H) % 8 == 0) ? 1 : 0;
   hipLaunchKernelGGL(attn_fwd40_kernel, dim3((unsigned)grid), dim3(X40_THREADS), X40_LDS, st, a, V, ldv, nqb, remap);
+  attn_rec(1, ATTN_FAM_FWD40, CL_BF16, X40_DH);
+  g_attn_last.fwd_frags = 4; g_attn_last.remap = remap; g_attn_last.grid_fwd = (int)grid;
   CL_CHECK_LAUNCH();
   return CL_OK;
 }

@@ -1302,6 +1302,7 @@ static int set_lds(K kern, int bytes) {
   return CL_OK;
 }
 
+AttnLaunchRec g_attn_last{};   // probe record (attention.h)
 int g_attn_variant_dkv4 = 0;   // probe hook: variant 21 = dK/dV with four key fragments per wave (fold kernels)
 int g_attn_variant = 0;    // probe hook (csrc/debug_hooks.h): 1 = tile-synchronous kernels only, 11 = backward with s_setprio,
                            // 13 / 14 = hybrid forward with fragment lookahead 3 / 2 (also: skip the pre-scaled-Q forward)
@@ -1318,6 +1319,8 @@ static int launch_fwd_hyb_t(const AttnFwdArgs& a, const void* V, long ldv, hipSt
   const long grid = (long)nqb * a.H * a.B;
   const int remap = ((a.B * a.H) % 8 == 0) ? 1 : 0;
   hipLaunchKernelGGL((attn_fwd_hyb_kernel<DH, LA>), dim3((unsigned)grid), dim3(512), LDS, st, a, V, ldv, nqb, remap);
+  attn_rec(1, ATTN_FAM_HYB, CL_BF16, DH);
+  g_attn_last.fwd_frags = 4; g_attn_last.lookahead = LA; g_attn_last.remap = remap; g_attn_last.grid_fwd = (int)grid;
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
@@ -1349,10 +1352,14 @@ static int launch_fwd_tr(const AttnFwdArgs& a, const void* V, long ldv, hipStrea
   if (QW == 2 && blocks128 >= 512) {
     dim3 grid((a.N + 127) / 128, a.H, a.B);
     hipLaunchKernelGGL((attn_fwd_tr_kernel<DH, QW, TAIL>), grid, dim3(256), LDS, st, a, V, ldv);
+    g_attn_last.fwd_frags = QW; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   } else {
     dim3 grid((a.N + 63) / 64, a.H, a.B);
     hipLaunchKernelGGL((attn_fwd_tr_kernel<DH, 1, TAIL>), grid, dim3(256), LDS, st, a, V, ldv);
+    g_attn_last.fwd_frags = 1; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   }
+  attn_rec(1, ATTN_FAM_TR, CL_BF16, DH);
+  g_attn_last.bits = TAIL ? ATTN_BIT_TAIL : 0;
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
@@ -1365,7 +1372,9 @@ static int launch_fwd_tr_t(const AttnFwdArgs& a, const void* V, long ldv, hipStr
 }
 
 int attn_fwd_tr(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st) {
+  attn_rec_begin();
   if ((a.ldq * 2) % 16 || (a.ldk * 2) % 16 || (ldv * 2) % 16 || (a.ldo * 2) % 16 || a.Nkv < 1 || a.N < 1) return CL_EINVAL;
+  if (a.LSE && (a.lse_stride % 64 || a.lse_stride < a.N)) return CL_EINVAL;   // as the backward: rows of neighbouring heads must not overlap
   // pre-scaled Q, d_head 40, whole blocks: the VALU-lean software-pipelined forward (attention_fwd40.hip)
   if (g_attn_variant == 0 && attn_fwd40_applies(a)) return attn_fwd40(a, V, ldv, st);
   switch (a.DH) {
@@ -1393,15 +1402,19 @@ static int launch_fwd_tr_ip(const AttnFwdArgs& a, const void* V, long ldv, const
   if (QW == 2 && blocks128 >= 512) {
     dim3 grid((a.N + 127) / 128, a.H, a.B);
     hipLaunchKernelGGL((attn_fwd_tr_ip_kernel<DH, QW>), grid, dim3(256), LDS, st, a, V, ldv, ip);
+    g_attn_last.fwd_frags = QW; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   } else {
     dim3 grid((a.N + 63) / 64, a.H, a.B);
     hipLaunchKernelGGL((attn_fwd_tr_ip_kernel<DH, 1>), grid, dim3(256), LDS, st, a, V, ldv, ip);
+    g_attn_last.fwd_frags = 1; g_attn_last.grid_fwd = (int)(grid.x * grid.y * grid.z);
   }
+  attn_rec(1, ATTN_FAM_TR_IP, CL_BF16, DH);
   CL_CHECK_LAUNCH();
   return CL_OK;
 }
 
 int attn_fwd_tr_ip(const AttnFwdArgs& a, const void* V, long ldv, const AttnIpArgs& ip, hipStream_t st) {
+  attn_rec_begin();
   if ((a.ldq * 2) % 16 || (a.ldk * 2) % 16 || (ldv * 2) % 16 || (a.ldo * 2) % 16 || a.Nkv < 1 || a.N < 1) return CL_EINVAL;
   if ((ip.ldk2 * 2) % 16 || (ip.ldv2 * 2) % 16 || ip.Nip < 1 || ip.Nip > 64 || !ip.K2 || !ip.V2 || a.LSE) return CL_EINVAL;
   switch (a.DH) {
@@ -1442,6 +1455,9 @@ static int launch_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
     if (rc) return rc;
   }
   const bool prio = g_attn_variant == 11;
+  attn_rec(2, ATTN_FAM_TR, CL_BF16, DH);
+  g_attn_last.bits = (TQ ? ATTN_BIT_TQ : 0) | (TK ? ATTN_BIT_TK : 0);
+  g_attn_last.delta_launch = fused_delta ? 0 : 1;
   // -lse / -delta folded into the matrix products: d_head 40, pre-scaled Q, whole tiles, row scratch given, enough
   // workgroups for the two-fragment forms (the 64x64 self-attentions)
   if constexpr (DH == 40 && !TQ && !TK) {
@@ -1456,6 +1472,7 @@ static int launch_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
         done_f = true;
       }
       hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, KF, TK, true, false, true>), dim3(a.N / 128, a.H, a.B), dim3(256), LDS_DQ3, st, a);
+      g_attn_last.family = ATTN_FAM_FOLD; g_attn_last.dq_frags = KF; g_attn_last.grid_dq = (int)qb2;
       if (a.dK) {
         // probe (cl_debug_attention_variant(21)): FOUR key fragments per wave (64 keys, one wave per SIMD: the Q / dO fragments of a
         // tile are read once per 64 keys instead of once per 32) -- VERDICT r5 item 4
@@ -1463,8 +1480,12 @@ static int launch_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
           static bool done4 = false;
           if (!done4) { if (set_lds(&attn_bwd_dkv_tr_kernel<DH, 4, TQ, false, true>, LDS_DKV3)) return CL_ELAUNCH; done4 = true; }
           hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, 4, TQ, false, true>), dim3(a.Nkv / 256, a.H, a.B), dim3(256), LDS_DKV3, st, a);
-        } else
-        hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, KF, TQ, false, true>), dim3(a.Nkv / 128, a.H, a.B), dim3(256), LDS_DKV3, st, a);
+          g_attn_last.dkv_frags = 4; g_attn_last.grid_dkv = (a.Nkv / 256) * a.H * a.B;
+        } else {
+          hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, KF, TQ, false, true>), dim3(a.Nkv / 128, a.H, a.B), dim3(256), LDS_DKV3, st, a);
+          g_attn_last.dkv_frags = KF; g_attn_last.grid_dkv = (int)kb2;
+        }
+        g_attn_last.dkv_ran = 1;
       }
       CL_CHECK_LAUNCH();
       return CL_OK;
@@ -1477,10 +1498,13 @@ static int launch_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
       if (fused_delta && prio) hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, KF, TK, true, true>), grid, dim3(256), LDS_DQ, st, a);
       else if (fused_delta) hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, KF, TK, true>), grid, dim3(256), LDS_DQ, st, a);
       else hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, KF, TK>), grid, dim3(256), LDS_DQ, st, a);
+      g_attn_last.dq_frags = KF; g_attn_last.grid_dq = (int)(grid.x * grid.y * grid.z);
+      if (fused_delta && prio) g_attn_last.bits |= ATTN_BIT_PRIO;
     } else {
       dim3 grid((a.N + 63) / 64, a.H, a.B);
       if (fused_delta) hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, 1, TK, true>), grid, dim3(256), LDS_DQ, st, a);
       else hipLaunchKernelGGL((attn_bwd_dq_tr_kernel<DH, 1, TK>), grid, dim3(256), LDS_DQ, st, a);
+      g_attn_last.dq_frags = 1; g_attn_last.grid_dq = (int)(grid.x * grid.y * grid.z);
     }
   };
   if (fused_delta) launch_dq();            // dQ (+ delta) first: the dK/dV kernel reads delta
@@ -1491,10 +1515,14 @@ static int launch_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
       dim3 grid((a.Nkv + 127) / 128, a.H, a.B);
       if (prio) hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, KF, TQ, true>), grid, dim3(256), LDS_DKV, st, a);
       else hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, KF, TQ>), grid, dim3(256), LDS_DKV, st, a);
+      g_attn_last.dkv_frags = KF; g_attn_last.grid_dkv = (int)(grid.x * grid.y * grid.z);
+      if (prio) g_attn_last.bits |= ATTN_BIT_PRIO;
     } else {
       dim3 grid((a.Nkv + 63) / 64, a.H, a.B);
       hipLaunchKernelGGL((attn_bwd_dkv_tr_kernel<DH, 1, TQ>), grid, dim3(256), LDS_DKV, st, a);
+      g_attn_last.dkv_frags = 1; g_attn_last.grid_dkv = (int)(grid.x * grid.y * grid.z);
     }
+    g_attn_last.dkv_ran = 1;
   }
   if (!fused_delta) launch_dq();
   CL_CHECK_LAUNCH();
@@ -1509,6 +1537,7 @@ static int launch_bwd_tr_t(const AttnBwdArgs& a, hipStream_t st) {
 }
 
 int attn_bwd_tr(const AttnBwdArgs& a, hipStream_t st) {
+  attn_rec_begin();
   if ((a.ldq * 2) % 16 || (a.ldk * 2) % 16 || (a.ldv * 2) % 16 || (a.lddo * 2) % 16 || (a.ldo * 2) % 16) return CL_EINVAL;
   if ((a.lddq * 2) % 16 || a.lse_stride % 64 || a.lse_stride < a.N) return CL_EINVAL;
   if ((a.dK == nullptr) != (a.dV == nullptr)) return CL_EINVAL;

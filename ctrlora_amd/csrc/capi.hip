@@ -53,6 +53,13 @@ int cl_debug_attention_variant(int v) {
   }
 }
 int cl_debug_attention_fuse_delta(int on) { g_attn_fuse_delta = on ? 1 : 0; return CL_OK; }
+int cl_debug_attention_last_launch(int* out16) {
+  static_assert(sizeof(AttnLaunchRec) == 16 * sizeof(int), "cl_debug_attention_last_launch: sixteen ints");
+  if (!out16) return CL_EINVAL;
+  const int* rec = reinterpret_cast<const int*>(&g_attn_last);
+  for (int i = 0; i < 16; ++i) out16[i] = rec[i];
+  return CL_OK;
+}
 int cl_debug_groupnorm_form(int three_pass, int one_pass) {
   g_gn_three_pass = three_pass ? 1 : 0; g_gn_one_pass = one_pass ? 1 : 0; return CL_OK;
 }
@@ -224,6 +231,7 @@ int cl_layernorm_bwd(int dtype, const void* x, long ldx, const void* dy, long ld
 int cl_attention_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* Vt, int nkv_pad,
                      void* O, long ldo, float* LSE, int lse_stride, int B, int H, int N, int Nkv, int dh, float scale,
                      void* stream) {
+  attn_rec_begin();
   AttnFwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.Vt = Vt; a.nkv_pad = nkv_pad; a.O = O; a.ldo = ldo;
   a.LSE = LSE; a.lse_stride = lse_stride; a.B = B; a.H = H; a.N = N; a.Nkv = Nkv; a.DH = dh; a.scale = scale;
   return attn_fwd(a, dtype, S(stream));
@@ -234,6 +242,7 @@ int cl_attention_bwd(int dtype, const void* Q, long ldq, const void* K, long ldk
                      const void* Kt, int nkv_pad, const float* LSE, float* Delta, int lse_stride, void* dQ, long lddq,
                      void* dK, long lddk, void* dV, long lddv, int B, int H, int N, int Nkv, int dh, float scale,
                      void* stream) {
+  attn_rec_begin();
   AttnBwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo;
   a.dO = dO; a.lddo = lddo; a.Qt = Qt; a.dOt = dOt; a.n_pad = n_pad; a.Kt = Kt; a.nkv_pad = nkv_pad; a.LSE = LSE;
   a.Delta = Delta; a.lse_stride = lse_stride; a.dQ = dQ; a.lddq = lddq; a.dK = dK; a.lddk = lddk; a.dV = dV; a.lddv = lddv;
@@ -244,6 +253,7 @@ int cl_attention_bwd(int dtype, const void* Q, long ldq, const void* K, long ldk
 int cl_attention_fwd_v2(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O,
                         long ldo, float* LSE, int lse_stride, int B, int H, int N, int Nkv, int dh, float scale,
                         int flags, void* stream) {
+  attn_rec_begin();
   if (dtype != CL_BF16 || (flags & ~CL_ATTN_Q_PRESCALED)) return CL_EINVAL;
   AttnFwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.O = O; a.ldo = ldo;
   a.LSE = LSE; a.lse_stride = lse_stride; a.B = B; a.H = H; a.N = N; a.Nkv = Nkv; a.DH = dh; a.scale = scale;
@@ -254,6 +264,7 @@ int cl_attention_fwd_v2(int dtype, const void* Q, long ldq, const void* K, long 
 int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                         const void* Kip, long ldkip, const void* Vip, long ldvip, void* O, long ldo, int B, int H, int N,
                         int Nkv, int Nip, int dh, float scale, float ip_scale, int flags, void* stream) {
+  attn_rec_begin();
   if (flags & ~CL_ATTN_Q_PRESCALED) return CL_EINVAL;
   AttnFwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.O = O; a.ldo = ldo;
   a.B = B; a.H = H; a.N = N; a.Nkv = Nkv; a.DH = dh; a.scale = scale;
@@ -269,6 +280,7 @@ int cl_attention_bwd_v2(int dtype, const void* Q, long ldq, const void* K, long 
                         const void* O, long ldo, const void* dO, long lddo, const float* LSE, float* Delta,
                         int lse_stride, void* dQ, long lddq, void* dK, long lddk, void* dV, long lddv, int B, int H,
                         int N, int Nkv, int dh, float scale, int flags, void* row_ws, void* stream) {
+  attn_rec_begin();
   if (dtype != CL_BF16 || (flags & ~CL_ATTN_Q_PRESCALED)) return CL_EINVAL;
   AttnBwdArgs a{}; a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.V = V; a.ldv = ldv; a.O = O; a.ldo = ldo;
   a.dO = dO; a.lddo = lddo; a.LSE = LSE; a.Delta = Delta; a.lse_stride = lse_stride; a.dQ = dQ; a.lddq = lddq;

@@ -125,6 +125,7 @@ EXPORTED = tuple(_SIGS.keys())
 _DEBUG_SIGS = {
     "cl_debug_attention_variant": [_I],
     "cl_debug_attention_fuse_delta": [_I],
+    "cl_debug_attention_last_launch": [_P],
     "cl_debug_groupnorm_form": [_I, _I],
     "cl_debug_groupnorm_coop": [_I],
     "cl_debug_groupnorm_coop_timeouts": [],

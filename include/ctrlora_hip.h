@@ -242,7 +242,8 @@ int cl_layernorm_bwd(int dtype, const void* x, long ldx, const void* dy, long ld
 /* ---- attention ----------------------------------------------------------------------- */
 /* CrossAttention.forward core (attention.py:171-192): softmax(q k^T d^-1/2) v per head, fp32
  * scores/softmax, never materialising the score matrix.  Vt / Qt / dOt / Kt are the
- * [B][H*dh][pad64] transposes made with cl_transpose. */
+ * [B][H*dh][pad64] transposes made with cl_transpose.  LSE (may be NULL in the forwards) is
+ * [B][H][lse_stride] fp32 with lse_stride a multiple of 64 and >= N; CL_EINVAL otherwise, in every entry point. */
 int cl_attention_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* Vt,
                      int nkv_pad, void* O, long ldo, float* LSE, int lse_stride, int B, int H, int N,
                      int Nkv, int dh, float scale, void* stream);
