@@ -63,6 +63,13 @@ int cl_debug_attention_last_launch(int* out16) {
 int cl_debug_groupnorm_form(int three_pass, int one_pass) {
   g_gn_three_pass = three_pass ? 1 : 0; g_gn_one_pass = one_pass ? 1 : 0; return CL_OK;
 }
+int cl_debug_norm_last_launch(int* out12) {
+  static_assert(sizeof(NormLaunchRec) == 12 * sizeof(int), "cl_debug_norm_last_launch: twelve ints");
+  if (!out12) return CL_EINVAL;
+  const int* rec = reinterpret_cast<const int*>(&g_norm_last);
+  for (int i = 0; i < 12; ++i) out12[i] = rec[i];
+  return CL_OK;
+}
 
 int cl_debug_groupnorm_coop(int on) { g_gn_coop = on ? 1 : 0; return CL_OK; }
 int cl_debug_groupnorm_coop_timeouts(void) { return (int)gnc_timeouts(); }

@@ -22,6 +22,15 @@ int cl_debug_attention_last_launch(int* out16);
 /* GroupNorm launch forms: three_pass = 1 forces partial -> finalize -> apply; one_pass = 0 disables the one-launch
  * register-resident form (defaults 0, 1) */
 int cl_debug_groupnorm_form(int three_pass, int one_pass);
+/* Read-only: what the last normalisation entry point of this process launched (csrc/norm.h: NormLaunchRec; host side only, no
+ * GPU touched).  out[0..11] = kind (0 nothing: the call was refused, 1 / 2 GroupNorm forward / backward, 3 / 4 LayerNorm forward /
+ * backward), form (1 one launch, 2 two launches, 3 three launches, 4 cooperative; LayerNorm backward: 2 = with the finishing
+ * kernel), dtype, NV (16-byte vectors per lane kept in registers; 0 for the chunked GroupNorm forms), LPR of the one-launch
+ * GroupNorm / PY of the chunked ones / rows per wave iteration of the LayerNorm backward, waves (one-launch GroupNorm) or threads
+ * per workgroup, CB (one-launch GroupNorm) / VX (chunked) / D / 8 (LayerNorm), pixel chunks per sample, grid x, grid y,
+ * column-sum path of the LayerNorm backward (0 none, 1 workspace + finishing kernel, 2 atomics), channel passes per lane.
+ * The cooperative form fills kind and form only.  CL_EINVAL for a null pointer. */
+int cl_debug_norm_last_launch(int* out12);
 /* 1 = GroupNorms whose groups span >= 1024 pixels run as one cooperative launch (csrc/norm_coop.hip: pixel slabs in
  * registers, the workgroups of a sample meet at a counter); 0 (default: measured no faster, see norm_coop.hip) = the forms above only.  _timeouts: how many workgroups ever gave
  * up waiting at that counter (0 unless something is broken; a timed-out launch produced wrong numbers) */

@@ -39,6 +39,28 @@ struct LnBwdArgs {
   float* dgamma; float* dbeta;
 };
 
+// Read-only record of what the last normalisation entry point launched (csrc/debug_hooks.h: cl_debug_norm_last_launch).
+// Host side only: every launcher of norm.hip fills it once CL_CHECK_LAUNCH has passed (norm_coop.hip only names its form); an
+// entry point that refuses its arguments, or whose launch fails (CL_ELAUNCH), leaves kind = 0.  No kernel, launch or argument
+// depends on it.
+enum { NORM_GN_FWD = 1, NORM_GN_BWD = 2, NORM_LN_FWD = 3, NORM_LN_BWD = 4 };
+enum { NORM_FORM_ONE = 1, NORM_FORM_TWO = 2, NORM_FORM_THREE = 3, NORM_FORM_COOP = 4 };
+struct NormLaunchRec {
+  int kind;          // 0 nothing launched (refused), NORM_GN_* / NORM_LN_*
+  int form;          // NORM_FORM_*: launches of the call (LayerNorm backward: 2 = kernel + ln_bwd_finish_kernel)
+  int dtype;
+  int nv;            // 16-byte vectors per lane held in registers (gn1_* / ln_*; 0 for the chunked GroupNorm forms)
+  int lpr_rpi;       // gn1_*: lanes per pixel row; chunked GroupNorm: PY; LayerNorm: rows per wave iteration
+  int threads;       // gn1_*: waves per workgroup; every other form: threads per workgroup
+  int cb_vx;         // gn1_*: channels per block CB; chunked GroupNorm: VX; LayerNorm: D / 8
+  int chunks;        // pixel chunks per sample (chunked GroupNorm forms)
+  int grid_x, grid_y;
+  int colsum;        // dgamma / dbeta of the LayerNorm backward: 0 none, 1 workspace + finish, 2 atomics
+  int passes;        // channel passes per lane (C / 8 / VX; 1 everywhere else)
+};
+extern NormLaunchRec g_norm_last;
+inline void norm_rec_begin() { g_norm_last = NormLaunchRec{}; }
+
 long gn_ws_floats(int B, int HW, int C);
 // one-launch, one-pass cooperative form (norm_coop.hip); CL_EINVAL = not its case
 extern int g_gn_coop;

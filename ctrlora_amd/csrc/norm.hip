@@ -21,6 +21,8 @@ namespace cl {
 
 static constexpr int GN_MAX_THREADS = 512;
 
+NormLaunchRec g_norm_last{};   // probe record (norm.h)
+
 struct GnGeom { int VX, PY, threads, nchunk, ppc; };
 
 static GnGeom gn_geom(int B, int HW, int C) {
@@ -324,6 +326,13 @@ template <> struct Pack8<float> {
 
 struct Gn1Geom { int CB, VX, LPR, NW, NV, nblk; bool ok; };
 
+static void gn_rec1(int kind, int dtype, const Gn1Geom& g, int B) {
+  g_norm_last = NormLaunchRec{kind, NORM_FORM_ONE, dtype, g.NV, g.LPR, g.NW, g.CB, 0, g.nblk, B, 0, 1};
+}
+static void gn_rec(int kind, int form, int dtype, const GnGeom& g, int B, int C) {
+  g_norm_last = NormLaunchRec{kind, form, dtype, 0, g.PY, g.threads, g.VX, g.nchunk, g.nchunk, B, 0, (C / 8 + g.VX - 1) / g.VX};
+}
+
 static Gn1Geom gn1_geom(int B, int HW, int C, int G, int esize, bool bwd) {
   Gn1Geom g{}; g.ok = false;
   if (!g_gn_one_pass || g_gn_three_pass || C % G) return g;
@@ -570,6 +579,7 @@ static int gn_fwd_t(const GnArgs& a, hipStream_t st) {
   if (g1.ok) {
     if (a.silu) gn1_fwd_launch<T, true>(a, g1, st); else gn1_fwd_launch<T, false>(a, g1, st);
     CL_CHECK_LAUNCH();
+    gn_rec1(NORM_GN_FWD, sizeof(T) == 2 ? CL_BF16 : CL_F32, g1, a.B);
     return CL_OK;
   }
   const GnGeom g = gn_geom(a.B, a.HW, a.C);
@@ -585,6 +595,7 @@ static int gn_fwd_t(const GnArgs& a, hipStream_t st) {
       hipLaunchKernelGGL((gn_gapply_kernel<T, false>), grid, dim3(g.threads), 0, st, (const T*)a.x, a.ldx, (T*)a.y, a.ldy,
                          a.HW, a.C, a.G, g.VX, g.PY, g.ppc, g.nchunk, a.eps, a.gamma, a.beta, a.ws, a.stats);
     CL_CHECK_LAUNCH();
+    gn_rec(NORM_GN_FWD, NORM_FORM_TWO, sizeof(T) == 2 ? CL_BF16 : CL_F32, g, a.B, a.C);
     return CL_OK;
   }
   float* partial = a.ws;
@@ -601,10 +612,12 @@ static int gn_fwd_t(const GnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((gn_apply_kernel<T, false>), grid, dim3(g.threads), 0, st,
                        (const T*)a.x, a.ldx, (T*)a.y, a.ldy, a.HW, a.C, g.VX, g.PY, g.ppc, coef);
   CL_CHECK_LAUNCH();
+  gn_rec(NORM_GN_FWD, NORM_FORM_THREE, sizeof(T) == 2 ? CL_BF16 : CL_F32, g, a.B, a.C);
   return CL_OK;
 }
 
 int gn_fwd(const GnArgs& a, int dtype, hipStream_t st) {
+  norm_rec_begin();
   if (a.C % 8 || a.C % a.G || a.ldx % 8 || a.ldy % 8 || a.C > 8192) return CL_EINVAL;
   if (a.C / 8 > 320 && (a.C / 8) % 320) return CL_EINVAL;  // uniform trip count across the block
   if (gnc_fwd(a, dtype, st) == CL_OK) return CL_OK;        // groups spanning >= 1024 pixels: one launch, one pass (norm_coop.hip)
@@ -861,6 +874,7 @@ static int gn_bwd_t(const GnBwdArgs& a, hipStream_t st) {
   if (g1.ok) {
     if (a.silu) gn1_bwd_launch<T, true>(a, g1, st); else gn1_bwd_launch<T, false>(a, g1, st);
     CL_CHECK_LAUNCH();
+    gn_rec1(NORM_GN_BWD, sizeof(T) == 2 ? CL_BF16 : CL_F32, g1, a.B);
     return CL_OK;
   }
   const GnGeom g = gn_geom(a.B, a.HW, a.C);
@@ -877,6 +891,7 @@ static int gn_bwd_t(const GnBwdArgs& a, hipStream_t st) {
     if (a.silu) { GN_BWD_G(true) } else { GN_BWD_G(false) }
 #undef GN_BWD_G
     CL_CHECK_LAUNCH();
+    gn_rec(NORM_GN_BWD, NORM_FORM_TWO, sizeof(T) == 2 ? CL_BF16 : CL_F32, g, a.B, a.C);
     return CL_OK;
   }
   float* partial = a.ws;
@@ -894,10 +909,12 @@ static int gn_bwd_t(const GnBwdArgs& a, hipStream_t st) {
   if (a.silu) { GN_BWD_LAUNCH(true) } else { GN_BWD_LAUNCH(false) }
 #undef GN_BWD_LAUNCH
   CL_CHECK_LAUNCH();
+  gn_rec(NORM_GN_BWD, NORM_FORM_THREE, sizeof(T) == 2 ? CL_BF16 : CL_F32, g, a.B, a.C);
   return CL_OK;
 }
 
 int gn_bwd(const GnBwdArgs& a, int dtype, hipStream_t st) {
+  norm_rec_begin();
   if (a.C % 8 || a.C % a.G || a.ldx % 8 || a.lddy % 8 || a.lddx % 8 || a.C > 8192) return CL_EINVAL;
   if (a.C / 8 > 320 && (a.C / 8) % 320) return CL_EINVAL;
   if (a.accum && a.ldacc % 8) return CL_EINVAL;
@@ -1106,6 +1123,7 @@ static int ln_grid(int M) {
 }
 
 int ln_fwd(const LnArgs& a, int dtype, hipStream_t st) {
+  norm_rec_begin();
   if (a.D % 8 || a.D > 64 * LN_MAXV * 8 || a.ldx % 8 || a.ldy % 8) return CL_EINVAL;
   if (dtype == CL_BF16)
     hipLaunchKernelGGL((ln_fwd_kernel<bf16_t>), dim3(ln_grid(a.M)), dim3(256), 0, st, (const bf16_t*)a.x, a.ldx,
@@ -1114,11 +1132,15 @@ int ln_fwd(const LnArgs& a, int dtype, hipStream_t st) {
     hipLaunchKernelGGL((ln_fwd_kernel<float>), dim3(ln_grid(a.M)), dim3(256), 0, st, (const float*)a.x, a.ldx,
                        (float*)a.y, a.ldy, a.M, a.D, a.eps, a.gamma, a.beta, a.stats);
   CL_CHECK_LAUNCH();
+  g_norm_last = NormLaunchRec{NORM_LN_FWD, NORM_FORM_ONE, dtype == CL_BF16 ? CL_BF16 : CL_F32, (a.D / 8 + 63) / 64, 1, 256, a.D / 8, 0,
+                              ln_grid(a.M), 1, 0, 1};
   return CL_OK;
 }
 
 int ln_bwd(const LnBwdArgs& a, int dtype, hipStream_t st) {
+  norm_rec_begin();
   if (a.D % 8 || a.D > 64 * LN_MAXV * 8 || a.ldx % 8 || a.lddy % 8 || a.lddx % 8) return CL_EINVAL;
+  if (a.accum && a.ldacc % 8) return CL_EINVAL;   // accum is read as 16-byte vectors like every other operand
   if ((a.dgamma == nullptr) != (a.dbeta == nullptr)) return CL_EINVAL;
   const int rpi = a.D <= 512 ? 4 : a.D <= 1024 ? 2 : 1;   // rows per wave iteration (see ln_bwd_kernel)
   int grid = (a.M + 4 * rpi - 1) / (4 * rpi);
@@ -1151,6 +1173,8 @@ int ln_bwd(const LnBwdArgs& a, int dtype, hipStream_t st) {
     hipLaunchKernelGGL(ln_bwd_finish_kernel, dim3((2 * a.D + 31) / 32), dim3(1024), 0, st, partial, grid, a.D,
                        a.dgamma, a.dbeta);
   CL_CHECK_LAUNCH();
+  g_norm_last = NormLaunchRec{NORM_LN_BWD, partial ? NORM_FORM_TWO : NORM_FORM_ONE, dtype == CL_BF16 ? CL_BF16 : CL_F32,
+                              a.D <= 512 ? 1 : a.D <= 1024 ? 2 : 3, rpi, 256, a.D / 8, 0, grid, 1, a.dgamma ? (partial ? 1 : 2) : 0, 1};
   return CL_OK;
 }
 

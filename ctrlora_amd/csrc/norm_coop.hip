@@ -387,6 +387,7 @@ int gnc_fwd(const GnArgs& a, int dtype, hipStream_t st) {
 #undef GNC_FWD_NV
 #undef GNC_FWD
   CL_CHECK_LAUNCH();
+  g_norm_last.kind = NORM_GN_FWD; g_norm_last.form = NORM_FORM_COOP;   // probe record (norm.h)
   return CL_OK;
 }
 
@@ -413,6 +414,7 @@ int gnc_bwd(const GnBwdArgs& a, int dtype, hipStream_t st) {
 #undef GNC_BWD_NV
 #undef GNC_BWD
   CL_CHECK_LAUNCH();
+  g_norm_last.kind = NORM_GN_BWD; g_norm_last.form = NORM_FORM_COOP;   // probe record (norm.h)
   return CL_OK;
 }
 

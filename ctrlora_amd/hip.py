@@ -127,6 +127,7 @@ _DEBUG_SIGS = {
     "cl_debug_attention_fuse_delta": [_I],
     "cl_debug_attention_last_launch": [_P],
     "cl_debug_groupnorm_form": [_I, _I],
+    "cl_debug_norm_last_launch": [_P],
     "cl_debug_groupnorm_coop": [_I],
     "cl_debug_groupnorm_coop_timeouts": [],
     "cl_debug_gemm_tag": [_I],

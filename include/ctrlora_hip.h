@@ -223,18 +223,41 @@ int cl_conv1x1_fwd(int dtype, const void* x, long ldx, const void* W, const floa
                    int M, int Cin, int Cout, void* stream);
 
 /* ---- normalisation ------------------------------------------------------------------- */
-/* GroupNorm32(32, C) [+ SiLU] in fp32 statistics (util.py:217-219; openaimodel.py:201-202). */
+/* GroupNorm32(groups, C) [+ SiLU] in fp32 statistics (util.py:217-219; openaimodel.py:201-202) over token-major
+ * [B * HW, C] operands.  cl_groupnorm_ws_floats(B, HW, C) floats of scratch in `ws` (either direction).
+ * cl_groupnorm_silu_fwd: y = silu?(gamma (x - mean) rstd + beta); stats [B][groups][2] = {mean, rstd} in fp32 is always
+ * written (the backward reads it).  Argument restrictions (CL_EINVAL otherwise, nothing launched, nothing written --
+ * tests/test_gpu_norm_conformance.py):
+ *   - C % 8 == 0, C % groups == 0, C <= 8192, and C / 8 <= 320 or a multiple of 320: C <= 2560, or C in {5120, 7680}
+ *     (C = 4096 is refused);
+ *   - ldx % 8 == 0 and ldy % 8 == 0 (rows are read and written as 16-byte vectors; x and y may be column slices of wider
+ *     buffers at an offset that is a multiple of 8 elements, and 16-byte aligned). */
 long cl_groupnorm_ws_floats(int B, int HW, int C);
 int cl_groupnorm_silu_fwd(int dtype, const void* x, long ldx, void* y, long ldy, const float* gamma,
                           const float* beta, int B, int HW, int C, int groups, float eps, int silu,
                           float* stats, float* ws, void* stream);
+/* cl_groupnorm_silu_bwd: dx = (accum ? accum : 0) + grad of the forward at dy, from x and the forward's stats; dgamma /
+ * dbeta (both or neither; fp32 [C]) are ACCUMULATED onto what they hold (fp32 atomics: not bit-reproducible).
+ * Argument restrictions (CL_EINVAL otherwise, nothing launched, nothing written):
+ *   - those of the forward on C and groups;
+ *   - ldx, lddy, lddx % 8 == 0, and ldacc % 8 == 0 when accum != NULL;
+ *   - dgamma and dbeta both NULL or both given. */
 int cl_groupnorm_silu_bwd(int dtype, const void* x, long ldx, const void* dy, long lddy,
                           const void* accum, long ldacc, void* dx, long lddx, const float* gamma,
                           const float* beta, const float* stats, int B, int HW, int C, int groups,
                           int silu, float* dgamma, float* dbeta, float* ws, void* stream);
-/* nn.LayerNorm over the last dim (attention.py:263-265) */
+/* nn.LayerNorm over the last dim (attention.py:263-265), two-pass fp32 statistics; stats (may be NULL) = [M][2] fp32
+ * {mean, rstd} for the backward.  Argument restrictions (CL_EINVAL otherwise, nothing launched, nothing written):
+ *   - D % 8 == 0 and D <= 1536 (a row lives in the registers of one wave);
+ *   - ldx % 8 == 0 and ldy % 8 == 0. */
 int cl_layernorm_fwd(int dtype, const void* x, long ldx, void* y, long ldy, const float* gamma,
                      const float* beta, int M, int D, float eps, float* stats, void* stream);
+/* dx = (accum ? accum : 0) + grad; dgamma / dbeta (both or neither; fp32 [D]) are ACCUMULATED onto what they hold: through
+ * the registered scratch + a finishing launch (deterministic) or, without one, fp32 atomics (cl_set_workspace).
+ * Argument restrictions (CL_EINVAL otherwise, nothing launched, nothing written):
+ *   - D % 8 == 0 and D <= 1536;
+ *   - ldx, lddy, lddx % 8 == 0, and ldacc % 8 == 0 when accum != NULL;
+ *   - dgamma and dbeta both NULL or both given. */
 int cl_layernorm_bwd(int dtype, const void* x, long ldx, const void* dy, long lddy, const void* accum,
                      long ldacc, void* dx, long lddx, const float* gamma, const float* stats, int M,
                      int D, float* dgamma, float* dbeta, void* stream);
