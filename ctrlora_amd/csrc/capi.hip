@@ -75,6 +75,17 @@ int cl_debug_groupnorm_coop(int on) { g_gn_coop = on ? 1 : 0; return CL_OK; }
 int cl_debug_groupnorm_coop_timeouts(void) { return (int)gnc_timeouts(); }
 
 int cl_debug_wgrad_ring(int slots) { if (slots != 3 && slots != 4 && slots != 6) return CL_EINVAL; g_wgrad_ring = slots; return CL_OK; }
+int cl_debug_wgrad_last_launch(int* out32) {
+  static_assert(sizeof(WgradLaunchRec) == 32 * sizeof(int), "cl_debug_wgrad_last_launch: thirty-two ints");
+  if (!out32) return CL_EINVAL;
+  const int* rec = reinterpret_cast<const int*>(&g_wgrad_last);
+  for (int i = 0; i < 32; ++i) out32[i] = rec[i];
+  return CL_OK;
+}
+int cl_debug_wgrad_last_problem(int i, long* out12) {
+  static_assert(sizeof(WgradProbRec) == 12 * sizeof(long), "cl_debug_wgrad_last_problem: twelve longs");
+  return wgrad_rec_problem(i, out12);
+}
 int cl_debug_gemm_xs_rules(int on) { g_gemm_xs_rules = on ? 1 : 0; return CL_OK; }
 int cl_debug_gemm_tag(int on) { g_gemm_tag_on = on ? 1 : 0; return CL_OK; }
 int cl_debug_gemm_tag_count(void) { return gemm_tag_count(); }
@@ -154,11 +165,13 @@ int cl_weight_grad(int dtype, const void* dyT, long lddyt, const void* xT, long 
 
 int cl_weight_grad_tn(int dtype, const void* dy, long lddy, const void* x, long ldx, float* dW, long lddw, int M,
                       int N, int K, float scale, const void* zero_page, void* stream) {
+  wgrad_rec_begin();
   if (dtype != CL_BF16) return CL_EINVAL;   // fp32 parity mode uses cl_transpose + cl_weight_grad
   return launch_wgrad_tn(dy, lddy, x, ldx, dW, lddw, M, N, K, scale, zero_page, S(stream));
 }
 
 int cl_weight_grad_tn_group(int dtype, int n, const cl_wgrad_desc* descs, const void* zero_page, void* stream) {
+  wgrad_rec_begin();
   if (dtype != CL_BF16) return CL_EINVAL;
   if (n <= 0) return CL_OK;
   if (!descs || n > 4096) return CL_EINVAL;

@@ -31,6 +31,17 @@ int cl_debug_groupnorm_form(int three_pass, int one_pass);
  * column-sum path of the LayerNorm backward (0 none, 1 workspace + finishing kernel, 2 atomics), channel passes per lane.
  * The cooperative form fills kind and form only.  CL_EINVAL for a null pointer. */
 int cl_debug_norm_last_launch(int* out12);
+/* Read-only: what the last weight-gradient entry point of this process (cl_weight_grad_tn, cl_weight_grad_tn_group) launched
+ * (csrc/gemm.h: WgradLaunchRec; host side only, no GPU touched).  out[0..31] = ran (0 nothing: the call was refused, failed or had
+ * nothing to add), launches of the single-product / single-tap kernel, of the row-of-three kernel, of the slab-reduce kernel,
+ * problems launched, group launches, LDS ring depth and rows of m per step of the last group, then for the first eight group
+ * launches (row-of-three kernel?, its grid, the reduce kernel's grid or 0).  CL_EINVAL for a null pointer.
+ * cl_debug_wgrad_last_problem(i, out): problem i of that call in launch order, out[0..11] = row-of-three kind?, 128 x 128 tiles,
+ * 32-row steps per split, splits, byte offset of its slabs in the workspace (-1: none, accumulated directly), first workgroup,
+ * first reduce workgroup, index of the group launch it went into, index of its descriptor in the caller's array, M, N, K.
+ * CL_EINVAL past the end (the record holds the first 4096 problems) or for a null pointer. */
+int cl_debug_wgrad_last_launch(int* out32);
+int cl_debug_wgrad_last_problem(int i, long* out12);
 /* 1 = GroupNorms whose groups span >= 1024 pixels run as one cooperative launch (csrc/norm_coop.hip: pixel slabs in
  * registers, the workgroups of a sample meet at a counter); 0 (default: measured no faster, see norm_coop.hip) = the forms above only.  _timeouts: how many workgroups ever gave
  * up waiting at that counter (0 unless something is broken; a timed-out launch produced wrong numbers) */

@@ -111,7 +111,29 @@ struct WgradDesc {
   const void* dy; long lddy; const void* x; long ldx; float* dW; long lddw; int M, N, K; float alpha;
   int tap, Hin, Win, Hout, Wout, stride, pad, reserved;
 };
+// Refused (CL_EINVAL, decided for every descriptor of both kinds before the first launch, so nothing has been accumulated): N or K
+// not a multiple of 8 or below 8; lddy / ldx not multiples of 8, lddw not a multiple of 4; lddy < N, ldx < K, lddw < K (3 K for
+// tap >= 16); dy, x or dW null, dW not 16-byte aligned; tap in 9 .. 15 or above 18; tap >= 0: Hin / Win / Hout / Wout outside
+// 1 .. 32767, pad outside 0 .. 32767, stride not 1 or 2, M not a multiple of Hout Wout; tap >= 16 also: stride != 1, pad != 1,
+// Hin != Hout, Win != Wout, M % 32, Wout neither a multiple of 32 nor 8 nor 16 (the x tile holds 40 rows: W < 8 needs 48 or more).
+// Descriptors with M, N or K <= 0 are skipped.
 int launch_wgrad_tn_group(const WgradDesc* probs, int n, const void* zero_page, hipStream_t stream);
+// Read-only record of what the last weight-gradient entry point launched (csrc/debug_hooks.h: cl_debug_wgrad_last_launch /
+// cl_debug_wgrad_last_problem); host side only.  All zero: the call was refused, failed or had nothing to launch.
+constexpr int WGRAD_REC_GROUPS = 8;
+struct WgradLaunchRec {
+  int ran;                 // 1 = at least one group was launched
+  int tn_launches, row3_launches, reduce_launches;
+  int problems, groups;    // problems launched, group launches (of either kernel)
+  int ring, rows;          // of the last group: LDS ring depth (8 for the row-of-three kernel), rows of m per step
+  int group[WGRAD_REC_GROUPS][3];   // the first eight group launches: row-of-three kernel?, its grid, the reduce kernel's grid (0 = none)
+};
+struct WgradProbRec {      // one problem as it went into a group's descriptor table (twelve longs)
+  long row3, tiles, per, splits, slab_off /* byte offset into the workspace, -1 = no slabs */, blk0, red0, group, desc, M, N, K;
+};
+extern WgradLaunchRec g_wgrad_last;
+void wgrad_rec_begin();
+int wgrad_rec_problem(int i, long* out12);
 extern int g_wgrad_blocks, g_wgrad_min_steps, g_wgrad_ring, g_wgrad_rows;
 extern int g_fl128_split_want, g_tiny_m_minsub;
 extern int g_fl_persist_stagger;

@@ -24,6 +24,7 @@
 #include "gemm.h"
 #include "mma.h"
 #include <algorithm>
+#include <vector>
 
 namespace cl {
 
@@ -221,7 +222,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(const WgradGroup grp, 
 // fragments one LDS row further on: a third of the dy traffic, 1.1x instead of 3x the x traffic, the dy fragment reads
 // shared by three batches.  8 waves (2 x 4) own a 128 (n) x 128 (k) tile of each of the three taps (wave: 64 x 32 per tap,
 // 96 accumulator registers); x tile = 40 LDS rows of 256 bytes, row of (step row r, tap kx) = (r / seg) (seg + 2) + r % seg + kx
-// with seg = min(W, 32) (40 rows at most; a step is 32 / seg whole image-row segments: W a multiple of 32, or 32 a multiple of W).
+// with seg = min(W, 32) (a step is 32 / seg whole image-row segments, (32 / seg) (seg + 2) = 32 + 64 / seg rows: 34 / 36 / 40 at
+// W >= 32 / 16 / 8, and 48 / 64 at W = 4 / 2, which the 40-row tile does not hold -- the launcher refuses W < 8).  W is a multiple
+// of 32, or 8 or 16.
 // dW points at tap (ky, 0) of the [N][3][3][K] gradient: tap kx lies K floats further on.
 template <int R>
 __global__ __launch_bounds__(512, 2) void wgrad_row3_kernel(const WgradGroup grp, const void* __restrict__ zero_page) {
@@ -440,7 +443,40 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradGroup grp)
 int g_wgrad_blocks = 512, g_wgrad_min_steps = 8, g_wgrad_ring = 3, g_wgrad_rows = 32;
 int g_wgrad_row3_blocks = 512;
 
+// Read-only record of what the last weight-gradient entry point launched (csrc/debug_hooks.h: cl_debug_wgrad_last_launch /
+// _last_problem; host side only).  Filled after the launch check of every group; reset by the entry points.
+WgradLaunchRec g_wgrad_last{};
+static std::vector<WgradProbRec> g_wgrad_last_probs;
+static std::vector<WgradProbRec> g_wgrad_pending;      // the problems of the group being assembled
+void wgrad_rec_begin() { g_wgrad_last = WgradLaunchRec{}; g_wgrad_last_probs.clear(); g_wgrad_pending.clear(); }
+int wgrad_rec_problem(int i, long* out12) {
+  if (!out12 || i < 0 || i >= (int)g_wgrad_last_probs.size()) return CL_EINVAL;
+  const long* rec = reinterpret_cast<const long*>(&g_wgrad_last_probs[i]);
+  for (int k = 0; k < 12; ++k) out12[k] = rec[k];
+  return CL_OK;
+}
+static void wgrad_rec_group(int nblocks, int nred, bool row3) {
+  WgradLaunchRec& r = g_wgrad_last;
+  r.ran = 1; r.ring = row3 ? 8 : g_wgrad_ring; r.rows = row3 ? 32 : (g_wgrad_rows == 64 ? 64 : 32);
+  (row3 ? r.row3_launches : r.tn_launches) += 1;
+  if (nred > 0) r.reduce_launches += 1;
+  if (r.groups < WGRAD_REC_GROUPS) { int* g = r.group[r.groups]; g[0] = row3 ? 1 : 0; g[1] = nblocks; g[2] = nred; }
+  for (WgradProbRec& p : g_wgrad_pending) {
+    p.group = r.groups;
+    if (g_wgrad_last_probs.size() < 4096) g_wgrad_last_probs.push_back(p);
+  }
+  r.problems += (int)g_wgrad_pending.size();
+  r.groups += 1;
+  g_wgrad_pending.clear();
+}
+
+static int launch_group_(WgradGroup& grp, int nblocks, int nred, const void* zero_page, hipStream_t stream, bool row3);
 static int launch_group(WgradGroup& grp, int nblocks, int nred, const void* zero_page, hipStream_t stream, bool row3 = false) {
+  const int rc = launch_group_(grp, nblocks, nred, zero_page, stream, row3);
+  if (rc == CL_OK) wgrad_rec_group(nblocks, nred, row3);
+  return rc;
+}
+static int launch_group_(WgradGroup& grp, int nblocks, int nred, const void* zero_page, hipStream_t stream, bool row3) {
   if (row3) {   // groups of row-of-three-taps problems (tap = 16 + ky): their own kernel, 8 waves, 72 KB ring
     static bool attr_set = false;
     // one 8-wave workgroup per CU (178 registers): the ring is what keeps DMA in flight -- 8 slots of 18 KB = seven steps ahead
@@ -488,14 +524,44 @@ static int launch_group(WgradGroup& grp, int nblocks, int nred, const void* zero
 // partial slabs of all problems are carved out of the registered workspace (group flushed early when it is full).
 static int launch_wgrad_group_kind(const WgradDesc* probs, int n, const void* zero_page, hipStream_t stream, bool row3);
 
+// What a descriptor must satisfy (include/ctrlora_hip.h: cl_wgrad_desc lists the same).  Decided for EVERY descriptor of a call,
+// of both kinds, before the first launch: a refused call has accumulated nothing.
+static bool wgrad_desc_ok(const WgradDesc& d) {
+  if (d.N % 8 || d.K % 8 || d.lddy % 8 || d.ldx % 8 || d.lddw % 4 || d.N < 8 || d.K < 8 ||
+      (reinterpret_cast<uintptr_t>(d.dW) & 15))
+    return false;
+  if (!d.dy || !d.x || !d.dW || d.lddy < d.N || d.ldx < d.K) return false;
+  if (d.tap >= 16) {   // tap = 16 + ky: the three taps of kernel row ky; stride 1, pad 1, a 32-row step = whole image-row segments
+    if (d.tap > 18 || d.stride != 1 || d.pad != 1 || d.Hin != d.Hout || d.Win != d.Wout || d.Hout <= 0 || d.Wout <= 0 ||
+        d.Hin > 32767 || d.Win > 32767 || d.M % ((long)d.Hout * d.Wout) || d.M % 32 ||
+        !((d.Wout % 32 == 0) || d.Wout == 8 || d.Wout == 16) || (d.K % 4) || d.lddw < 3L * d.K)
+      return false;
+    return true;
+  }
+  if (d.lddw < d.K) return false;   // rows of dW would overlap: every workgroup reads, adds and writes its tile unsynchronised
+  if (d.tap > 8 || (d.tap >= 0 && (d.Hin <= 0 || d.Win <= 0 || d.Hout <= 0 || d.Wout <= 0 || d.Hin > 32767 || d.Win > 32767 ||
+                                   d.Hout > 32767 || d.Wout > 32767 || d.pad < 0 || d.pad > 32767 ||
+                                   d.stride < 1 || d.stride > 2 || d.M % ((long)d.Hout * d.Wout))))
+    return false;
+  return true;
+}
+
 int launch_wgrad_tn_group(const WgradDesc* probs, int n, const void* zero_page, hipStream_t stream) {
+  wgrad_rec_begin();
   if (n <= 0) return CL_OK;
   if (!zero_page) return CL_EINVAL;
   bool any3 = false, any1 = false;
-  for (int i = 0; i < n; ++i) (probs[i].tap >= 16 ? any3 : any1) = true;
-  if (any1) { const int rc = launch_wgrad_group_kind(probs, n, zero_page, stream, false); if (rc) return rc; }
-  if (any3) return launch_wgrad_group_kind(probs, n, zero_page, stream, true);
-  return CL_OK;
+  for (int i = 0; i < n; ++i) {
+    const WgradDesc& d = probs[i];
+    (d.tap >= 16 ? any3 : any1) = true;
+    if (d.M <= 0 || d.N <= 0 || d.K <= 0) continue;   // nothing to add
+    if (!wgrad_desc_ok(d)) return CL_EINVAL;
+  }
+  int rc = CL_OK;
+  if (any1) rc = launch_wgrad_group_kind(probs, n, zero_page, stream, false);
+  if (!rc && any3) rc = launch_wgrad_group_kind(probs, n, zero_page, stream, true);
+  if (rc) wgrad_rec_begin();   // a call that failed reports nothing, like a refused one
+  return rc;
 }
 
 // one kind of problem per launch: single products / single taps (wgrad_tn_kernel) or rows of three taps (wgrad_row3_kernel)
@@ -508,21 +574,7 @@ static int launch_wgrad_group_kind(const WgradDesc* probs, int n, const void* ze
     const WgradDesc& d = probs[i];
     if ((d.tap >= 16) != row3) continue;
     if (d.M <= 0 || d.N <= 0 || d.K <= 0) continue;
-    if (d.N % 8 || d.K % 8 || d.lddy % 8 || d.ldx % 8 || d.lddw % 4 || d.N < 8 || d.K < 8 ||
-        (reinterpret_cast<uintptr_t>(d.dW) & 15))
-      return CL_EINVAL;
-    if (row3) {   // tap = 16 + ky: the three taps of kernel row ky; stride 1, pad 1, a 32-row step = whole image-row segments
-      if (d.tap > 18 || d.stride != 1 || d.pad != 1 || d.Hin != d.Hout || d.Win != d.Wout || d.Hout <= 0 || d.Wout <= 0 ||
-          d.Hin > 32767 || d.Win > 32767 || d.M % (d.Hout * d.Wout) || d.M % 32 ||
-          !((d.Wout % 32 == 0) || (d.Wout < 32 && 32 % d.Wout == 0)) || (d.K % 4) || d.lddw < 3L * d.K)
-        return CL_EINVAL;
-      tiles_all += (long)((d.N + 127) / 128) * ((d.K + 127) / 128);
-      continue;
-    }
-    if (d.tap > 8 || (d.tap >= 0 && (d.Hin <= 0 || d.Win <= 0 || d.Hout <= 0 || d.Wout <= 0 || d.Hin > 32767 || d.Win > 32767 ||
-                                     d.stride < 1 || d.stride > 2 || d.M % (d.Hout * d.Wout))))
-      return CL_EINVAL;
-    tiles_all += (long)((d.N + 127) / 128) * ((d.K + 127) / 128);
+    tiles_all += (long)((d.N + 127) / 128) * ((d.K + 127) / 128);   // (validated by launch_wgrad_tn_group)
   }
   if (tiles_all == 0) return CL_OK;
   // uniform number of m-steps per workgroup across the group (a step = g_wgrad_rows rows of m)
@@ -576,6 +628,8 @@ static int launch_wgrad_group_kind(const WgradDesc* probs, int n, const void* ze
     P.blk0 = nblocks; P.red0 = nred;
     P.tap = d.tap; P.Hin = (short)d.Hin; P.Win = (short)d.Win; P.Hout = (short)d.Hout; P.Wout = (short)d.Wout;
     P.stride = (short)d.stride; P.pad = (short)d.pad;
+    g_wgrad_pending.push_back(WgradProbRec{row3 ? 1L : 0L, (long)(tn * tk), (long)pp, (long)splits, splits > 1 ? ws_used : -1L,
+                                           (long)P.blk0, (long)P.red0, 0L, (long)i, (long)d.M, (long)d.N, (long)d.K});
     nblocks += tn * tk * splits;
     if (splits > 1) nred += (int)(((long)NT * d.N * (d.K / 4) + 255) / 256);
     ws_used += (need + 255) & ~255L;

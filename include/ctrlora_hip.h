@@ -196,10 +196,17 @@ typedef struct cl_wgrad_desc {
    * cldm/cldm_ctrlora_pretrain.py:174-182).  x is then the NHWC input [B*Hin*Win, K]; row m = (b, oy, ox) of dy pairs
    * with input pixel (oy*stride + tap/3 - pad, ox*stride + tap%3 - pad), zero outside the image; dW points at the tap's
    * [N, K] slice of a [N][3][3][K] gradient (lddw = 9 K).  tap = -1: plain dy^T x (the other fields are ignored).
-   * tap = 16 + ky (stride 1, pad 1, Wout a multiple of 32 or a divisor of 32, M a multiple of 32): the THREE taps (ky, 0..2) of a
+   * tap = 16 + ky (stride 1, pad 1, Wout a multiple of 32 or 8 or 16, M a multiple of 32): the THREE taps (ky, 0..2) of a
    * kernel row from one problem -- dW points at tap (ky, 0), taps kx = 1, 2 lie K and 2 K floats further on in each row. */
   int tap, Hin, Win, Hout, Wout, stride, pad, reserved;
 } cl_wgrad_desc;
+/* Refused with CL_EINVAL (cl_weight_grad_tn as the one-descriptor case with tap = -1): dtype not bf16; zero_page null; descs null or
+ * n > 4096; N or K not a multiple of 8 or below 8; lddy / ldx not multiples of 8, lddw not a multiple of 4; lddy < N, ldx < K,
+ * lddw < K (lddw < 3 K for tap >= 16); dy, x or dW null, dW not 16-byte aligned; tap in 9 .. 15 or above 18; with tap >= 0: Hin, Win,
+ * Hout or Wout outside 1 .. 32767, pad outside 0 .. 32767, stride not 1 or 2, M not a multiple of Hout Wout; with tap >= 16 also:
+ * stride != 1, pad != 1, Hin != Hout, Win != Wout, M not a multiple of 32, Wout neither a multiple of 32 nor 8 nor 16 (Wout = 4, 2, 1
+ * were accepted before and computed a wrong gradient).  Every descriptor is checked before anything is launched: a refused call has
+ * accumulated into NO dW of the group.  Descriptors with M, N or K <= 0 are skipped. */
 int cl_weight_grad_tn_group(int dtype, int n, const cl_wgrad_desc* descs, const void* zero_page, void* stream);
 
 /* 3x3 convolutions of ResBlock / Downsample / Upsample / input conv / out conv
