@@ -86,6 +86,13 @@ int cl_debug_wgrad_last_problem(int i, long* out12) {
   static_assert(sizeof(WgradProbRec) == 12 * sizeof(long), "cl_debug_wgrad_last_problem: twelve longs");
   return wgrad_rec_problem(i, out12);
 }
+int cl_debug_ew_last_launch(int* out8) {
+  static_assert(sizeof(EwLaunchRec) == 8 * sizeof(int), "cl_debug_ew_last_launch: eight ints");
+  if (!out8) return CL_EINVAL;
+  const int* rec = reinterpret_cast<const int*>(&g_ew_last);
+  for (int i = 0; i < 8; ++i) out8[i] = rec[i];
+  return CL_OK;
+}
 int cl_debug_gemm_xs_rules(int on) { g_gemm_xs_rules = on ? 1 : 0; return CL_OK; }
 int cl_debug_gemm_tag(int on) { g_gemm_tag_on = on ? 1 : 0; return CL_OK; }
 int cl_debug_gemm_tag_count(void) { return gemm_tag_count(); }

@@ -42,6 +42,14 @@ int cl_debug_norm_last_launch(int* out12);
  * CL_EINVAL past the end (the record holds the first 4096 problems) or for a null pointer. */
 int cl_debug_wgrad_last_launch(int* out32);
 int cl_debug_wgrad_last_problem(int i, long* out12);
+/* Read-only: what the last elementwise / layout entry point of this process (every launcher of csrc/elementwise.hip) launched
+ * (csrc/elementwise.h: EwLaunchRec; host side only, no GPU touched).  out[0..7] = entry point (EW_* of elementwise.h; 0 nothing:
+ * the call was refused, failed or had nothing to launch), dtype (-1: the entry point takes none), grid x, y, z and threads per
+ * workgroup of its main kernel, form, aux.  form / aux -- colsum: 1 = block partials through the workspace + finishing kernel,
+ * 2 = fp32 atomics, aux = pixel chunks per sample; zero: bit 0 = head bytes, bit 1 = tail bytes, aux = 16-byte vectors;
+ * vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups; transpose: dtype is the OUTPUT's, form = the input's
+ * dtype (CL_BF16 / CL_F32).  CL_EINVAL for a null pointer. */
+int cl_debug_ew_last_launch(int* out8);
 /* 1 = GroupNorms whose groups span >= 1024 pixels run as one cooperative launch (csrc/norm_coop.hip: pixel slabs in
  * registers, the workgroups of a sample meet at a counter); 0 (default: measured no faster, see norm_coop.hip) = the forms above only.  _timeouts: how many workgroups ever gave
  * up waiting at that counter (0 unless something is broken; a timed-out launch produced wrong numbers) */

@@ -4,6 +4,26 @@
 
 namespace cl {
 
+// Read-only record of what the last elementwise / layout entry point launched (csrc/debug_hooks.h: cl_debug_ew_last_launch).
+// Every launcher resets it on entry and ew_done() (elementwise.hip) writes it after the launch check, so a refused or failed
+// call leaves id = 0.  form / aux: colsum 1 = block partials + finishing kernel, 2 = atomics, aux = pixel chunks; zero: bit 0 =
+// head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
+// transpose: form = the input's dtype.
+enum {
+  EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
+  EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
+  EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
+  EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS
+};
+struct EwLaunchRec {
+  int id;        // EW_* of the entry point, 0 = nothing launched
+  int dtype;     // CL_BF16 / CL_F32 of the typed launchers (transpose: the output's), -1 where there is no dtype argument
+  int gx, gy, gz, threads;   // grid and workgroup size of the (main) kernel
+  int form, aux;
+};
+extern EwLaunchRec g_ew_last;
+inline void ew_rec_begin() { g_ew_last = EwLaunchRec{}; }
+
 int geglu_fwd(int dtype, const void* h, long ldh, void* out, long ldo, long M, int F, hipStream_t st);
 int geglu_bwd(int dtype, const void* h, long ldh, const void* dout, long lddo, void* dh, long lddh, long M, int F, hipStream_t st);
 int silu_fwd(int dtype, const void* x, void* y, long n, hipStream_t st);

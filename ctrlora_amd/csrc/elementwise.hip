@@ -628,141 +628,218 @@ __global__ void vit_tokens_kernel(const T* __restrict__ patch, long ldp, const f
 }
 
 // ================================================================= host launchers
+// Every launcher decides its refusals (CL_EINVAL; listed per entry point in include/ctrlora_hip.h) on the host before anything is
+// launched, and keeps a read-only record of what it launched (elementwise.h: EwLaunchRec): reset on entry, written by ew_done()
+// after the launch check.  Null pointers are refused only where the call has work to do: an empty call (n == 0, what an empty
+// tensor's null data pointer comes with) stays CL_OK.
+EwLaunchRec g_ew_last{};
+
+static inline bool bad_dtype(int dtype) { return dtype != CL_BF16 && dtype != CL_F32; }
+static inline bool mis16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+static int ew_done(int id, int dtype, dim3 grid, int threads, int form = 0, long aux = 0) {
+  CL_CHECK_LAUNCH();
+  g_ew_last = EwLaunchRec{id, dtype, (int)grid.x, (int)grid.y, (int)grid.z, threads, form, (int)(aux < 0x7fffffffL ? aux : 0x7fffffffL)};
+  return CL_OK;
+}
+
 int vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, hipStream_t st) {
+  ew_rec_begin();
+  if (bad_dtype(dtype) || !pixels || !out) return CL_EINVAL;
   if (B < 1 || C < 1 || P < 1 || S < P || S % P || Kpad % 8 || Kpad < C * P * P || ldo < Kpad || ldo % 8) return CL_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(pixels) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return CL_EINVAL;
-  const int grid = ew_grid((long)B * (S / P) * (S / P) * (Kpad / 8));
+  if (mis16(pixels) || mis16(out)) return CL_EINVAL;
+  const dim3 grid(ew_grid((long)B * (S / P) * (S / P) * (Kpad / 8)));
   const bool pair = P % 2 == 0 && S % 2 == 0;
-#define VIT_PR(T, PAIR) hipLaunchKernelGGL((vit_patch_rows_kernel<T, PAIR>), dim3(grid), dim3(256), 0, st, pixels, (T*)out, ldo, B, C, S, P, Kpad)
+#define VIT_PR(T, PAIR) hipLaunchKernelGGL((vit_patch_rows_kernel<T, PAIR>), grid, dim3(256), 0, st, pixels, (T*)out, ldo, B, C, S, P, Kpad)
   if (dtype == CL_BF16) { if (pair) VIT_PR(bf16_t, true); else VIT_PR(bf16_t, false); }
-  else if (dtype == CL_F32) { if (pair) VIT_PR(float, true); else VIT_PR(float, false); }
-  else return CL_EINVAL;
+  else { if (pair) VIT_PR(float, true); else VIT_PR(float, false); }
 #undef VIT_PR
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_VIT_PATCH_ROWS, dtype, grid, 256, pair ? 1 : 0);
 }
 int vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
                int D, hipStream_t st) {
+  ew_rec_begin();
+  if (bad_dtype(dtype) || !patch || !cls || !pos || !out) return CL_EINVAL;
   if (B < 1 || T < 2 || D < 8 || D % 8 || ldp % 8 || ldo % 8 || ldp < D || ldo < D) return CL_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(patch) & 15) || (reinterpret_cast<uintptr_t>(cls) & 15) || (reinterpret_cast<uintptr_t>(pos) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 15))
-    return CL_EINVAL;
-  const int grid = ew_grid((long)B * T * (D / 8));
-  if (dtype == CL_BF16) hipLaunchKernelGGL((vit_tokens_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)patch, ldp, cls, pos, (bf16_t*)out, ldo, B, T, D);
-  else if (dtype == CL_F32) hipLaunchKernelGGL((vit_tokens_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)patch, ldp, cls, pos, (float*)out, ldo, B, T, D);
-  else return CL_EINVAL;
-  CL_CHECK_LAUNCH(); return CL_OK;
+  if (mis16(patch) || mis16(cls) || mis16(pos) || mis16(out)) return CL_EINVAL;
+  const dim3 grid(ew_grid((long)B * T * (D / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((vit_tokens_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)patch, ldp, cls, pos, (bf16_t*)out, ldo, B, T, D);
+  else hipLaunchKernelGGL((vit_tokens_kernel<float>), grid, dim3(256), 0, st, (const float*)patch, ldp, cls, pos, (float*)out, ldo, B, T, D);
+  return ew_done(EW_VIT_TOKENS, dtype, grid, 256);
 }
 int geglu_fwd(int dtype, const void* h, long ldh, void* out, long ldo, long M, int F, hipStream_t st) {
-  if (F % 8 || ldh % 8 || ldo % 8) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((geglu_fwd_kernel<bf16_t>), dim3(ew_grid(M * (F / 8))), dim3(256), 0, st, (const bf16_t*)h, ldh, (bf16_t*)out, ldo, M, F);
-  else hipLaunchKernelGGL((geglu_fwd_kernel<float>), dim3(ew_grid(M * (F / 8))), dim3(256), 0, st, (const float*)h, ldh, (float*)out, ldo, M, F);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || M < 0 || F < 0 || F % 8 || ldh % 8 || ldo % 8 || ldh < 2L * F || ldo < F) return CL_EINVAL;
+  if (M * F > 0 && (!h || !out)) return CL_EINVAL;
+  if (mis16(h) || mis16(out)) return CL_EINVAL;
+  const dim3 grid(ew_grid(M * (F / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((geglu_fwd_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)h, ldh, (bf16_t*)out, ldo, M, F);
+  else hipLaunchKernelGGL((geglu_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)h, ldh, (float*)out, ldo, M, F);
+  return ew_done(EW_GEGLU_FWD, dtype, grid, 256);
 }
 int geglu_bwd(int dtype, const void* h, long ldh, const void* dout, long lddo, void* dh, long lddh, long M, int F, hipStream_t st) {
-  if (F % 8 || ldh % 8 || lddo % 8 || lddh % 8) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((geglu_bwd_kernel<bf16_t>), dim3(ew_grid(M * (F / 8))), dim3(256), 0, st, (const bf16_t*)h, ldh, (const bf16_t*)dout, lddo, (bf16_t*)dh, lddh, M, F);
-  else hipLaunchKernelGGL((geglu_bwd_kernel<float>), dim3(ew_grid(M * (F / 8))), dim3(256), 0, st, (const float*)h, ldh, (const float*)dout, lddo, (float*)dh, lddh, M, F);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || M < 0 || F < 0 || F % 8 || ldh % 8 || lddo % 8 || lddh % 8 || ldh < 2L * F || lddo < F || lddh < 2L * F) return CL_EINVAL;
+  if (M * F > 0 && (!h || !dout || !dh)) return CL_EINVAL;
+  if (mis16(h) || mis16(dout) || mis16(dh)) return CL_EINVAL;
+  const dim3 grid(ew_grid(M * (F / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((geglu_bwd_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)h, ldh, (const bf16_t*)dout, lddo, (bf16_t*)dh, lddh, M, F);
+  else hipLaunchKernelGGL((geglu_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)h, ldh, (const float*)dout, lddo, (float*)dh, lddh, M, F);
+  return ew_done(EW_GEGLU_BWD, dtype, grid, 256);
 }
 int silu_fwd(int dtype, const void* x, void* y, long n, hipStream_t st) {
-  if (n % 8) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((silu_fwd_kernel<bf16_t>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, n / 8);
-  else hipLaunchKernelGGL((silu_fwd_kernel<float>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const float*)x, (float*)y, n / 8);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || n < 0 || n % 8) return CL_EINVAL;
+  if (n > 0 && (!x || !y)) return CL_EINVAL;
+  if (mis16(x) || mis16(y)) return CL_EINVAL;
+  const dim3 grid(ew_grid(n / 8));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((silu_fwd_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, n / 8);
+  else hipLaunchKernelGGL((silu_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (float*)y, n / 8);
+  return ew_done(EW_SILU_FWD, dtype, grid, 256);
 }
 int silu_bwd(int dtype, const void* x, const void* dy, void* dx, long n, hipStream_t st) {
-  if (n % 8) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((silu_bwd_kernel<bf16_t>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n / 8);
-  else hipLaunchKernelGGL((silu_bwd_kernel<float>), dim3(ew_grid(n / 8)), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, n / 8);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || n < 0 || n % 8) return CL_EINVAL;
+  if (n > 0 && (!x || !dy || !dx)) return CL_EINVAL;
+  if (mis16(x) || mis16(dy) || mis16(dx)) return CL_EINVAL;
+  const dim3 grid(ew_grid(n / 8));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((silu_bwd_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n / 8);
+  else hipLaunchKernelGGL((silu_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, n / 8);
+  return ew_done(EW_SILU_BWD, dtype, grid, 256);
 }
 int axpby(int dtype, const void* x, long ldx, void* y, long ldy, long M, int C, float a, float b, hipStream_t st) {
-  if (C % 8 || ldx % 8 || ldy % 8) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((axpby_kernel<bf16_t>), dim3(ew_grid(M * (C / 8))), dim3(256), 0, st, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, M, C, a, b);
-  else hipLaunchKernelGGL((axpby_kernel<float>), dim3(ew_grid(M * (C / 8))), dim3(256), 0, st, (const float*)x, ldx, (float*)y, ldy, M, C, a, b);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || M < 0 || C < 0 || C % 8 || ldx % 8 || ldy % 8 || ldx < C || ldy < C) return CL_EINVAL;
+  if (M * C > 0 && (!x || !y)) return CL_EINVAL;
+  if (mis16(x) || mis16(y)) return CL_EINVAL;
+  const dim3 grid(ew_grid(M * (C / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((axpby_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, M, C, a, b);
+  else hipLaunchKernelGGL((axpby_kernel<float>), grid, dim3(256), 0, st, (const float*)x, ldx, (float*)y, ldy, M, C, a, b);
+  return ew_done(EW_AXPBY, dtype, grid, 256);
+}
+// the 64-tile kernels put the batch in grid.z (at most 65535) and the column tiles in grid.y
+static inline bool bad_tile_grid(int batch, int rows, int cols) {
+  return batch < 1 || batch > 65535 || rows < 1 || cols < 1 || (cols + 63) / 64 > 65535;
 }
 int transpose(int in_dtype, int out_dtype, const void* in, long ldi, long bsi, void* out, long ldo, long bso,
               int Bt, int R, int C, int Rpad, hipStream_t st) {
-  if (Rpad < R || ldo < Rpad) return CL_EINVAL;
-  dim3 grid((Rpad + 63) / 64, (C + 63) / 64, Bt);
+  ew_rec_begin();
+  if (Rpad < R || ldo < Rpad || bad_tile_grid(Bt, R, C) || !in || !out) return CL_EINVAL;
+  const dim3 grid((Rpad + 63) / 64, (C + 63) / 64, Bt);
   if (in_dtype == CL_F32 && out_dtype == CL_BF16) hipLaunchKernelGGL((transpose_kernel<float, bf16_t>), grid, dim3(256), 0, st, (const float*)in, ldi, bsi, (bf16_t*)out, ldo, bso, R, C, Rpad);
   else if (in_dtype == CL_F32 && out_dtype == CL_F32) hipLaunchKernelGGL((transpose_kernel<float, float>), grid, dim3(256), 0, st, (const float*)in, ldi, bsi, (float*)out, ldo, bso, R, C, Rpad);
   else if (in_dtype == CL_BF16 && out_dtype == CL_BF16) hipLaunchKernelGGL((transpose_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)in, ldi, bsi, (bf16_t*)out, ldo, bso, R, C, Rpad);
   else return CL_EINVAL;
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_TRANSPOSE, out_dtype, grid, 256, in_dtype);
 }
 int nchw_to_tok(int dtype, const float* in, void* out, long ldo, int B, int Cin, int Cpad, int HW, hipStream_t st) {
-  if (Cpad < Cin || ldo < Cpad) return CL_EINVAL;
-  dim3 grid((HW + 63) / 64, (Cpad + 63) / 64, B);
+  ew_rec_begin();
+  if (bad_dtype(dtype) || Cpad < Cin || ldo < Cpad || bad_tile_grid(B, HW, Cpad) || Cin < 1 || !in || !out) return CL_EINVAL;
+  const dim3 grid((HW + 63) / 64, (Cpad + 63) / 64, B);
   if (dtype == CL_BF16) hipLaunchKernelGGL((nchw_to_tok_kernel<bf16_t>), grid, dim3(256), 0, st, in, (bf16_t*)out, ldo, Cin, Cpad, HW);
   else hipLaunchKernelGGL((nchw_to_tok_kernel<float>), grid, dim3(256), 0, st, in, (float*)out, ldo, Cin, Cpad, HW);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_NCHW_TO_TOK, dtype, grid, 256);
 }
 int tok_to_nchw(int dtype, const void* in, long ldi, float* out, int B, int C, int HW, float alpha, float beta, hipStream_t st) {
-  dim3 grid((HW + 63) / 64, (C + 63) / 64, B);
+  ew_rec_begin();
+  if (bad_dtype(dtype) || bad_tile_grid(B, HW, C) || !in || !out) return CL_EINVAL;
+  const dim3 grid((HW + 63) / 64, (C + 63) / 64, B);
   if (dtype == CL_BF16) hipLaunchKernelGGL((tok_to_nchw_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)in, ldi, out, C, HW, alpha, beta);
   else hipLaunchKernelGGL((tok_to_nchw_kernel<float>), grid, dim3(256), 0, st, (const float*)in, ldi, out, C, HW, alpha, beta);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_TOK_TO_NCHW, dtype, grid, 256);
+}
+// both embeddings index with int: B half must be in [1, INT_MAX]
+static inline bool bad_embed(int dtype, const void* t, const float* freqs, const void* out, long ldo, int B, int half) {
+  return bad_dtype(dtype) || B < 1 || half < 1 || (long)B * half > 0x7fffffffL || ldo < 2L * half || !t || !freqs || !out;
 }
 int timestep_embed(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st) {
+  ew_rec_begin();
+  if (bad_embed(dtype, t, freqs, out, ldo, B, half)) return CL_EINVAL;
   const int n = B * half;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((timestep_embed_kernel<bf16_t>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (bf16_t*)out, ldo, B, half);
-  else hipLaunchKernelGGL((timestep_embed_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  const dim3 grid((n + 255) / 256);
+  if (dtype == CL_BF16) hipLaunchKernelGGL((timestep_embed_kernel<bf16_t>), grid, dim3(256), 0, st, t, freqs, (bf16_t*)out, ldo, B, half);
+  else hipLaunchKernelGGL((timestep_embed_kernel<float>), grid, dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
+  return ew_done(EW_TIMESTEP, dtype, grid, 256);
 }
 int timestep_embed_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st) {
+  ew_rec_begin();
+  if (bad_embed(dtype, t, freqs, out, ldo, B, half)) return CL_EINVAL;
   const int n = B * half;
-  if (n < 1) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((timestep_embed_f_kernel<bf16_t>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (bf16_t*)out, ldo, B, half);
-  else hipLaunchKernelGGL((timestep_embed_f_kernel<float>), dim3((n + 255) / 256), dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  const dim3 grid((n + 255) / 256);
+  if (dtype == CL_BF16) hipLaunchKernelGGL((timestep_embed_f_kernel<bf16_t>), grid, dim3(256), 0, st, t, freqs, (bf16_t*)out, ldo, B, half);
+  else hipLaunchKernelGGL((timestep_embed_f_kernel<float>), grid, dim3(256), 0, st, t, freqs, (float*)out, ldo, B, half);
+  return ew_done(EW_TIMESTEP_F, dtype, grid, 256);
 }
 int qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
             float* out, int B, long per, hipStream_t st) {
-  hipLaunchKernelGGL(qsample_kernel, dim3(ew_grid(B * per)), dim3(256), 0, st, z, noise, t, sqrt_ac, sqrt_1mac, out, per, (long)B * per);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (B < 0 || per < 0) return CL_EINVAL;
+  const long n = (long)B * per;
+  if (n > 0 && (!z || !noise || !t || !sqrt_ac || !sqrt_1mac || !out)) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(qsample_kernel, grid, dim3(256), 0, st, z, noise, t, sqrt_ac, sqrt_1mac, out, per, n);
+  return ew_done(EW_QSAMPLE, -1, grid, 256);
 }
 int mse_loss(const float* eps, const float* target, float* d_eps, float* loss, long n, float gscale, hipStream_t st) {
+  ew_rec_begin();
+  if (n < 0 || !loss || (n > 0 && (!eps || !target))) return CL_EINVAL;
   if (int rc = zero_bytes(loss, sizeof(float), st)) return rc;
-  hipLaunchKernelGGL(mse_kernel, dim3(ew_grid(n) < 256 ? ew_grid(n) : 256), dim3(256), 0, st, eps, target, d_eps, loss, n, gscale);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  const dim3 grid(ew_grid(n) < 256 ? ew_grid(n) : 256);
+  hipLaunchKernelGGL(mse_kernel, grid, dim3(256), 0, st, eps, target, d_eps, loss, n, gscale);
+  return ew_done(EW_MSE, -1, grid, 256, 0, grid.x);
 }
 int ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef, int index,
               float scale, float* x_prev, float* pred_x0, long n, hipStream_t st) {
-  hipLaunchKernelGGL(ddim_step_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, noise, coef, index, scale, x_prev, pred_x0, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (n < 0 || index < 0 || !coef || (n > 0 && (!x || !e_c || !x_prev))) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(ddim_step_kernel, grid, dim3(256), 0, st, x, e_c, e_u, noise, coef, index, scale, x_prev, pred_x0, n);
+  return ew_done(EW_DDIM_STEP, -1, grid, 256);
 }
 int adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
           float wd, int step, float gscale, hipStream_t st) {
+  ew_rec_begin();
+  if (n < 0 || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), gscale);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(adamw_kernel, grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), gscale);
+  return ew_done(EW_ADAMW, -1, grid, 256);
 }
 int plosses_mse(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
                 float* per_sample, float* scratch, int B, long per, float gscale, float w_simple, float w_elbo,
                 hipStream_t st) {
-  if (B < 1 || per < 1) return CL_EINVAL;
+  ew_rec_begin();
+  if (B < 1 || B > 65535 || per < 1) return CL_EINVAL;
+  if (!eps || !target || !out || !scratch || (lvlb && !t)) return CL_EINVAL;
   // d loss / d eps with loss = w_simple * mean(...) (the elbo term is not differentiated: weight 0 in every config)
   const float gmul = 2.0f * gscale * w_simple / ((float)per * (float)B);
-  hipLaunchKernelGGL(plosses_partial_kernel, dim3(PL_CHUNKS, B), dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
+  const dim3 grid(PL_CHUNKS, B);
+  hipLaunchKernelGGL(plosses_partial_kernel, grid, dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
   hipLaunchKernelGGL(plosses_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, out, per_sample, B, per, w_simple, w_elbo);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_PLOSSES, -1, grid, 256);
 }
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
                     int C, int tap, int stride, int pad, hipStream_t st) {
-  if (C % 8 || ldx % 8 || ldo % 8 || tap < 0 || tap > 8) return CL_EINVAL;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || C % 8 || ldx % 8 || ldo % 8 || tap < 0 || tap > 8) return CL_EINVAL;
+  if (stride < 1 || B < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || C < 8 || ldx < C || ldo < C) return CL_EINVAL;
+  if (!x || !out || mis16(x) || mis16(out)) return CL_EINVAL;
   const long total = (long)B * Hout * Wout * (C / 8);
-  if (dtype == CL_BF16) hipLaunchKernelGGL((conv_tap_gather_kernel<bf16_t>), dim3(ew_grid(total)), dim3(256), 0, st, (const bf16_t*)x, ldx, (bf16_t*)out, ldo, Hin, Win, Hout, Wout, C / 8, tap, stride, pad, total);
-  else hipLaunchKernelGGL((conv_tap_gather_kernel<float>), dim3(ew_grid(total)), dim3(256), 0, st, (const float*)x, ldx, (float*)out, ldo, Hin, Win, Hout, Wout, C / 8, tap, stride, pad, total);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  const dim3 grid(ew_grid(total));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((conv_tap_gather_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, ldx, (bf16_t*)out, ldo, Hin, Win, Hout, Wout, C / 8, tap, stride, pad, total);
+  else hipLaunchKernelGGL((conv_tap_gather_kernel<float>), grid, dim3(256), 0, st, (const float*)x, ldx, (float*)out, ldo, Hin, Win, Hout, Wout, C / 8, tap, stride, pad, total);
+  return ew_done(EW_CONV_TAP, dtype, grid, 256);
 }
 int softmax_rows(int dtype, const float* S, long lds_, void* P, long ldp, long M, int N, float scale, hipStream_t st) {
-  if (N % 4 || N > 8192 || lds_ % 4 || ldp % 4 || M <= 0) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((softmax_rows_kernel<bf16_t>), dim3((unsigned)M), dim3(256), 0, st, S, lds_, (bf16_t*)P, ldp, N, scale);
-  else hipLaunchKernelGGL((softmax_rows_kernel<float>), dim3((unsigned)M), dim3(256), 0, st, S, lds_, (float*)P, ldp, N, scale);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || N % 4 || N < 4 || N > 8192 || lds_ % 4 || ldp % 4 || lds_ < N || ldp < N || M <= 0 || M > 0x7fffffffL) return CL_EINVAL;
+  // float4 loads of S; a row of P is stored 4 elements at a time: 8 bytes in bf16, 16 in fp32
+  if (!S || !P || mis16(S) || (reinterpret_cast<uintptr_t>(P) & (dtype == CL_BF16 ? 7 : 15))) return CL_EINVAL;
+  const dim3 grid((unsigned)M);
+  if (dtype == CL_BF16) hipLaunchKernelGGL((softmax_rows_kernel<bf16_t>), grid, dim3(256), 0, st, S, lds_, (bf16_t*)P, ldp, N, scale);
+  else hipLaunchKernelGGL((softmax_rows_kernel<float>), grid, dim3(256), 0, st, S, lds_, (float*)P, ldp, N, scale);
+  return ew_done(EW_SOFTMAX, dtype, grid, 256);
 }
 // Clears are KERNEL nodes, not hipMemsetAsync: a step captured as SEVERAL consecutive hipGraphs in one memory pool
 // (the data-parallel segments, train.py) replayed memset nodes of small buffers out of order with their neighbours on
@@ -777,56 +854,83 @@ __global__ __launch_bounds__(256) void zero_kernel(unsigned char* __restrict__ p
   if (i0 < tail) p[head + nvec * 16 + i0] = 0;
 }
 int zero_bytes(void* p, long nbytes, hipStream_t st) {
+  ew_rec_begin();
   if (nbytes <= 0) return CL_OK;
+  if (!p) return CL_EINVAL;
   long head = (long)((16 - ((uintptr_t)p & 15)) & 15);
   if (head > nbytes) head = nbytes;
   const long nvec = (nbytes - head) / 16, tail = nbytes - head - nvec * 16;
-  hipLaunchKernelGGL(zero_kernel, dim3(ew_grid(nvec > 16 ? nvec : 16)), dim3(256), 0, st, (unsigned char*)p, head, nvec, tail);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  const dim3 grid(ew_grid(nvec > 16 ? nvec : 16));
+  hipLaunchKernelGGL(zero_kernel, grid, dim3(256), 0, st, (unsigned char*)p, head, nvec, tail);
+  return ew_done(EW_ZERO, -1, grid, 256, (head ? 1 : 0) | (tail ? 2 : 0), nvec);
 }
 int tick(int* counter, hipStream_t st) {
+  ew_rec_begin();
+  if (!counter) return CL_EINVAL;
   hipLaunchKernelGGL(tick_kernel, dim3(1), dim3(1), 0, st, counter);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_TICK, -1, dim3(1), 1);
 }
 int adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, hipStream_t st) {
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, st, p, g, m, v, n, hyper, step);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (n < 0 || !hyper || !step || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step);
+  return ew_done(EW_ADAMW_DEV, -1, grid, 256);
 }
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st) {
+  ew_rec_begin();
+  if (!table || !cursor || (n > 0 && !ts)) return CL_EINVAL;
   hipLaunchKernelGGL(ddim_set_t_kernel, dim3(1), dim3(256), 0, st, table, cursor, S, ts, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_DDIM_SET_T, -1, dim3(1), 256);
 }
 int ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                   const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, hipStream_t st) {
-  hipLaunchKernelGGL(ddim_step_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, noise, coef, cursor, S, scale, x_prev, pred_x0, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (n < 0 || !coef || !cursor || (n > 0 && (!x || !e_c || !x_prev))) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(ddim_step_dev_kernel, grid, dim3(256), 0, st, x, e_c, e_u, noise, coef, cursor, S, scale, x_prev, pred_x0, n);
+  return ew_done(EW_DDIM_STEP_DEV, -1, grid, 256);
 }
 int dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S, float scale,
                float* hist, float* x_next, float* pred_x0, long n, hipStream_t st) {
+  ew_rec_begin();
   if (S < 1 || index < 0 || index >= S || n < 1) return CL_EINVAL;
-  hipLaunchKernelGGL(dpmpp_step_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  if (!x || !e_c || !coef || !hist || !x_next) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(dpmpp_step_kernel, grid, dim3(256), 0, st, x, e_c, e_u, coef, index, scale, hist, x_next, pred_x0, n);
+  return ew_done(EW_DPMPP_STEP, -1, grid, 256);
 }
 int dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
                    float scale, float* hist, float* x_next, float* pred_x0, long n, hipStream_t st) {
+  ew_rec_begin();
   if (S < 1 || n < 1) return CL_EINVAL;
-  hipLaunchKernelGGL(dpmpp_step_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, e_c, e_u, coef, cursor, S, scale, hist, x_next, pred_x0, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  if (!x || !e_c || !coef || !cursor || !hist || !x_next) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(dpmpp_step_dev_kernel, grid, dim3(256), 0, st, x, e_c, e_u, coef, cursor, S, scale, hist, x_next, pred_x0, n);
+  return ew_done(EW_DPMPP_STEP_DEV, -1, grid, 256);
 }
 int dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, hipStream_t st) {
-  if (S < 1 || n < 1) return CL_EINVAL;
+  ew_rec_begin();
+  if (S < 1 || n < 1 || !coef || !cursor || !ts) return CL_EINVAL;
   hipLaunchKernelGGL(dpm_set_t_kernel, dim3(1), dim3(256), 0, st, coef, cursor, S, ts, n);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_DPM_SET_T, -1, dim3(1), 256);
 }
 int pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, hipStream_t st) {
-  if (C % 8 || ldi % 8 || ldo % 8) return CL_EINVAL;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || B < 0 || H < 0 || W < 0 || C < 0 || C % 8 || ldi % 8 || ldo % 8 || ldi < C || ldo < C) return CL_EINVAL;
   const long n = (long)B * H * W * (C / 8);
-  if (dtype == CL_BF16) hipLaunchKernelGGL((pool2x2_kernel<bf16_t>), dim3(ew_grid(n)), dim3(256), 0, st, (const bf16_t*)in, ldi, (bf16_t*)out, ldo, B, H, W, C, accumulate);
-  else hipLaunchKernelGGL((pool2x2_kernel<float>), dim3(ew_grid(n)), dim3(256), 0, st, (const float*)in, ldi, (float*)out, ldo, B, H, W, C, accumulate);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  if (n > 0 && (!in || !out)) return CL_EINVAL;
+  if (mis16(in) || mis16(out)) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((pool2x2_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)in, ldi, (bf16_t*)out, ldo, B, H, W, C, accumulate);
+  else hipLaunchKernelGGL((pool2x2_kernel<float>), grid, dim3(256), 0, st, (const float*)in, ldi, (float*)out, ldo, B, H, W, C, accumulate);
+  return ew_done(EW_POOL2X2, dtype, grid, 256);
 }
 int colsum(int dtype, const void* in, long ldi, float* out, long ldo, int B, int HW, int C, float scale, hipStream_t st) {
-  if (C % 8 || ldi % 8) return CL_EINVAL;
+  ew_rec_begin();
+  // (B and HW divide below; B is grid.y)
+  if (bad_dtype(dtype) || B < 1 || B > 65535 || HW < 1 || C < 8 || C % 8 || ldi % 8 || ldi < C || ldo < C) return CL_EINVAL;
+  if (!in || !out || mis16(in)) return CL_EINVAL;
   int nchunk = (HW + 63) / 64;
   int want = (512 + B - 1) / B;
   if (nchunk > want) nchunk = want;
@@ -842,13 +946,16 @@ int colsum(int dtype, const void* in, long ldi, float* out, long ldo, int B, int
   else hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, st, (const float*)in, ldi, out, ldo, HW, C, ppc, scale, partial);
   if (partial)
     hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 31) / 32, B), dim3(1024), 0, st, partial, nchunk, C, out, ldo, scale);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  return ew_done(EW_COLSUM, dtype, grid, 256, partial ? 1 : 2, nchunk);
 }
 int pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R, int C, int Cpad, hipStream_t st) {
-  if (Cpad < C || ldo < Cpad) return CL_EINVAL;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((pack_kernel<bf16_t>), dim3(ew_grid(R * Cpad)), dim3(256), 0, st, in, ldi, (bf16_t*)out, ldo, R, C, Cpad);
-  else hipLaunchKernelGGL((pack_kernel<float>), dim3(ew_grid(R * Cpad)), dim3(256), 0, st, in, ldi, (float*)out, ldo, R, C, Cpad);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  ew_rec_begin();
+  if (bad_dtype(dtype) || R < 0 || C < 0 || Cpad < C || ldo < Cpad || ldi < C) return CL_EINVAL;
+  if (R * Cpad > 0 && (!out || (C > 0 && !in))) return CL_EINVAL;
+  const dim3 grid(ew_grid(R * Cpad));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((pack_kernel<bf16_t>), grid, dim3(256), 0, st, in, ldi, (bf16_t*)out, ldo, R, C, Cpad);
+  else hipLaunchKernelGGL((pack_kernel<float>), grid, dim3(256), 0, st, in, ldi, (float*)out, ldo, R, C, Cpad);
+  return ew_done(EW_PACK2D, dtype, grid, 256);
 }
 
 // ------------------------------------------------------------------ fused re-pack of the trainables
@@ -897,10 +1004,14 @@ __global__ __launch_bounds__(256) void repack_kernel(const float* __restrict__ f
 
 int repack(int dtype, const float* flat, const long* desc, const int* tile_prefix, int ndesc, int total_tiles,
            hipStream_t st) {
+  ew_rec_begin();
+  if (bad_dtype(dtype)) return CL_EINVAL;
   if (ndesc <= 0 || total_tiles <= 0) return CL_OK;
-  if (dtype == CL_BF16) hipLaunchKernelGGL((repack_kernel<bf16_t>), dim3(total_tiles), dim3(256), 0, st, flat, desc, tile_prefix, ndesc);
-  else hipLaunchKernelGGL((repack_kernel<float>), dim3(total_tiles), dim3(256), 0, st, flat, desc, tile_prefix, ndesc);
-  CL_CHECK_LAUNCH(); return CL_OK;
+  if (!flat || !desc || !tile_prefix) return CL_EINVAL;
+  const dim3 grid(total_tiles);
+  if (dtype == CL_BF16) hipLaunchKernelGGL((repack_kernel<bf16_t>), grid, dim3(256), 0, st, flat, desc, tile_prefix, ndesc);
+  else hipLaunchKernelGGL((repack_kernel<float>), grid, dim3(256), 0, st, flat, desc, tile_prefix, ndesc);
+  return ew_done(EW_REPACK, dtype, grid, 256);
 }
 
 }  // namespace cl

@@ -135,6 +135,7 @@ _DEBUG_SIGS = {
     "cl_debug_wgrad_ring": [_I],
     "cl_debug_wgrad_last_launch": [_P],
     "cl_debug_wgrad_last_problem": [_I, _P],
+    "cl_debug_ew_last_launch": [_P],
     "cl_debug_gemm_tag_count": [],
     "cl_debug_gemm_tag_clear": [],
     "cl_debug_gemm_tag_get": [_I, _P],

@@ -314,15 +314,27 @@ int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long 
  * 3 instead of 5 vector instructions per score pair).  Results are the same with or without it. */
 
 /* ---- elementwise / layout ------------------------------------------------------------ */
+/* Every entry point below decides its refusals on the host: CL_EINVAL, nothing launched, nothing written.  Common to all of them:
+ * a dtype other than CL_BF16 / CL_F32 where there is a dtype argument, and a null required pointer (optional ones are named; a call
+ * with nothing to do -- n == 0, M == 0 -- returns CL_OK whatever its pointers).  The rest is listed per entry point. */
+/* cl_geglu_fwd / _bwd: F % 8, a leading dimension % 8, ldh < 2 F, ldo (lddo) < F, lddh < 2 F, M < 0, a base pointer not 16-byte aligned.
+ * cl_silu_fwd / _bwd: n % 8, n < 0, a pointer not 16-byte aligned.  cl_axpby: C % 8, ldx / ldy % 8 or < C, M < 0, a pointer not
+ * 16-byte aligned; y is not read when b == 0. */
 int cl_geglu_fwd(int dtype, const void* h, long ldh, void* out, long ldo, long M, int F, void* stream); /* attention.py:55-56 */
 int cl_geglu_bwd(int dtype, const void* h, long ldh, const void* dout, long lddo, void* dh, long lddh, long M, int F, void* stream);
 int cl_silu_fwd(int dtype, const void* x, void* y, long n, void* stream);
 int cl_silu_bwd(int dtype, const void* x, const void* dy, void* dx, long n, void* stream);
 int cl_axpby(int dtype, const void* x, long ldx, void* y, long ldy, long M, int C, float a, float b, void* stream);
+/* cl_transpose ([Bt][R][C] -> [Bt][C][Rpad], rows [R, Rpad) zero), cl_nchw_to_tok, cl_tok_to_nchw: a dtype pair other than
+ * fp32 -> bf16, fp32 -> fp32, bf16 -> bf16; Rpad < R, ldo < Rpad (Cpad < Cin, ldo < Cpad); a batch outside 1 .. 65535 (it is grid.z); an
+ * empty dimension (R, C, Cin, HW < 1); more than 65535 column tiles.  cl_tok_to_nchw does not read out when beta == 0. */
 int cl_transpose(int in_dtype, int out_dtype, const void* in, long ldi, long bsi, void* out, long ldo,
                  long bso, int Bt, int R, int C, int Rpad, void* stream);
 int cl_nchw_to_tok(int dtype, const float* in, void* out, long ldo, int B, int Cin, int Cpad, int HW, void* stream);
 int cl_tok_to_nchw(int dtype, const void* in, long ldi, float* out, int B, int C, int HW, float alpha, float beta, void* stream);
+/* cl_colsum: B outside 1 .. 65535, HW < 1, C < 8, C % 8, ldi % 8, ldi < C, ldo < C, in not 16-byte aligned.
+ * cl_pool2x2: C % 8, ldi / ldo % 8 or < C, a negative dimension, a pointer not 16-byte aligned; out is not read when accumulate == 0.
+ * cl_pack2d: Cpad < C, ldo < Cpad, ldi < C, R < 0. */
 /* out[b][c] += scale * sum_p in[b*HW + p][c]  (zero-conv bias gradients, time-embedding gradients) */
 int cl_colsum(int dtype, const void* in, long ldi, float* out, long ldo, int B, int HW, int C, float scale, void* stream);
 int cl_pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, void* stream);
@@ -349,6 +361,7 @@ int cl_vit_tokens(int dtype, const void* patch, long ldp, const float* cls, cons
  * tiles before matrix i (ndesc + 1 entries). */
 int cl_repack(int dtype, const float* flat, const long* desc, const int* tile_prefix, int ndesc,
               int total_tiles, void* stream);
+/* Both embeddings refuse B < 1, half < 1, B half > INT_MAX and ldo < 2 half. */
 /* timestep_embedding (util.py:154-174); freqs = the fp32 table exp(-ln(1e4) * arange(half)/half) */
 int cl_timestep_embedding(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, void* stream);
 /* The same embedding at floating-point times (added in ABI 7, compatible): the argument is t[b] * freqs[j] in fp32, cos | sin
@@ -359,13 +372,19 @@ int cl_timestep_embedding_f(int dtype, const float* t, const float* freqs, void*
 /* out[m, :] = x[pixel(m, tap), :] (zero outside the image), m = (b, oy, ox), pixel = (oy*stride + tap/3 - pad,
  * ox*stride + tap%3 - pad): the shifted operand of one tap of a 3x3 conv weight gradient, materialised (fp32 parity
  * mode; the bf16 weight-gradient kernel gathers in its own addressing, see cl_wgrad_desc.tap). */
+/* Refused: C % 8, C < 8, ldx / ldo % 8 or < C, tap outside 0 .. 8, stride < 1, an empty dimension (B, Hin, Win, Hout, Wout < 1), a
+ * pointer not 16-byte aligned. */
 int cl_conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout,
                        int Wout, int C, int tap, int stride, int pad, void* stream);
 /* Row softmax for the VAE's single-head attention (ldm/modules/diffusionmodules/model.py:183-186): fp32 scores
  * S [M, N] (row stride lds) -> `dtype` probabilities P [M, N] (row stride ldp), P = softmax(S * scale) per row. */
+/* Refused: N % 4, N < 4, N > 8192, lds / ldp % 4 or < N, M < 1, S not 16-byte aligned, P not 8-byte (bf16) / 16-byte (fp32) aligned. */
 int cl_softmax_rows(int dtype, const float* S, long lds, void* P, long ldp, long M, int N, float scale, void* stream);
 
 /* ---- diffusion bookkeeping ------------------------------------------------------------ */
+/* Refusals of the entry points below, besides null required pointers (optional: d_eps, e_u, noise, pred_x0, lvlb, per_sample): a
+ * negative n / B / per_sample; cl_p_losses_mse B outside 1 .. 65535, per_sample_elems < 1, lvlb without t; cl_ddim_step index < 0;
+ * cl_adamw_dev needs hyper and step even when n == 0.  cl_zero(p, 0) is CL_OK. */
 /* DDPM.q_sample (ddpm.py:356-359): out = sqrt_ac[t_b] * z + sqrt_1mac[t_b] * noise */
 int cl_qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
                float* out, int B, long per_sample, void* stream);
