@@ -8,8 +8,11 @@
   ip_scale_state        (:131-172 load_state_dict_ip) the per-layer ip_scale entries of the app's three targets
   CLIPVisionEncoder     (:387-391) the IP-Adapter image encoder, CLIPVisionModelWithProjection, built from its config; on a GPU
                         under no_grad it runs on the HIP engine (ctrlora_amd/engine/vit.py)
-  style_image_tokens    (:392-409) style image -> CLIPImageProcessor -> image_embeds -> ImageProjModel: the conditional and
-                        the unconditional (zero-embeds) tokens that go in as c_ip
+  CLIPTextEncoder       (:395-400) the text side of the same CLIP, CLIPTextModelWithProjection, built from its config; on a GPU
+                        under no_grad it runs on the HIP engine (ctrlora_amd/engine/clip_text.py)
+  style_image_tokens    (:392-409) style image -> CLIPImageProcessor -> image_embeds [- scale * the negative content prompt's
+                        text_embeds (:401-403)] -> ImageProjModel: the conditional and the unconditional (zero-embeds) tokens
+                        that go in as c_ip
 """
 import os
 from types import SimpleNamespace
@@ -160,11 +163,101 @@ class CLIPVisionEncoder(nn.Module):
         return SimpleNamespace(image_embeds=emb.clone(), hidden_states=tuple(hs))
 
 
-def style_image_tokens(encoder, image_proj, images, processor=None):
+# the text tower of the same OpenCLIP ViT-H/14 (laion/CLIP-ViT-H-14-laion2B-s32B-b79K in HF layout, the model the app loads)
+VIT_H_14_TEXT = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                     max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=1024)
+
+
+def _text_config(config):
+    from transformers import CLIPTextConfig
+    if config is None:
+        return CLIPTextConfig(**VIT_H_14_TEXT)
+    if isinstance(config, CLIPTextConfig):
+        return config
+    if isinstance(config, dict):
+        return CLIPTextConfig(**config)
+    if isinstance(config, (str, os.PathLike)) and os.path.isdir(config):       # a model directory: config.json only
+        import json
+        with open(os.path.join(config, "config.json")) as f:
+            d = json.load(f)
+        d = d.get("text_config", d)
+        known = CLIPTextConfig().to_dict()
+        return CLIPTextConfig(**{k: v for k, v in d.items() if k in known and k not in ("model_type", "transformers_version")})
+    raise TypeError(f"config: a CLIPTextConfig, a dict or a directory with config.json, not {type(config).__name__}")
+
+
+class CLIPTextEncoder(nn.Module):
+    """CLIPTextModelWithProjection under HF's own state-dict keys (`text_model.*`, `text_projection.weight`).  Built from a
+    config (default: the ViT-H/14 text tower), never from a hub name: nothing is downloaded, the weights come from
+    load_state_dict.  On a GPU under no_grad, with a config the executor covers (ctrlora_amd/engine/clip_text.py: check_config)
+    and no padding mask, forward runs on the HIP engine in `engine_dtype` (bf16 unless set_engine_dtype / CTRLORA_ENGINE_DTYPE
+    says fp32); otherwise (CPU, autograd, other configs, use_engine = False) it is the plain HF module."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        from transformers import CLIPTextModelWithProjection
+        self.config = _text_config(config)
+        hf = CLIPTextModelWithProjection(self.config).eval()
+        self.text_model, self.text_projection = hf.text_model, hf.text_projection              # HF's keys, no extra prefix
+        self.__dict__["_hf"] = hf                                                              # (not a registered child)
+        self.engine_dtype = None
+        self.use_engine = True
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
+
+    def set_engine_dtype(self, dtype):
+        self.engine_dtype = dtype
+        self.invalidate_engine()
+
+    def invalidate_engine(self):
+        self.__dict__.pop("_txt", None)
+
+    def _refresh_engine(self):
+        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
+        ex = self.__dict__.get("_txt")
+        if ex is not None:
+            if ex.device != next(self.parameters()).device:
+                self.invalidate_engine()
+            else:
+                ex.load(self.state_dict())
+
+    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
+        self.invalidate_engine()
+        return super()._apply(fn, *args, **kwargs)
+
+    def engine(self):
+        ex = self.__dict__.get("_txt")
+        if ex is None:
+            from ctrlora_amd.engine.clip_text import ClipTextE
+            dtype = self.engine_dtype
+            if dtype is None:
+                env = os.environ.get("CTRLORA_ENGINE_DTYPE", "bf16").lower()
+                dtype = torch.float32 if env in ("f32", "fp32", "float32") else torch.bfloat16
+            ex = ClipTextE(self.state_dict(), self.config, dtype, next(self.parameters()).device)
+            self.__dict__["_txt"] = ex
+        return ex
+
+    def _on_engine(self, input_ids, attention_mask):
+        from ctrlora_amd.engine.clip_text import supported
+        return (self.use_engine and input_ids.is_cuda and not torch.is_grad_enabled() and supported(self.config, attention_mask)
+                and input_ids.dim() == 2 and 1 <= input_ids.shape[1] <= self.config.max_position_embeddings)
+
+    def forward(self, input_ids, attention_mask=None):
+        """An object with .text_embeds [B, projection_dim] and .last_hidden_state [B, N, hidden_size] (fresh tensors in the
+        parameters' dtype)."""
+        if not self._on_engine(input_ids, attention_mask):
+            return self._hf(input_ids=input_ids, attention_mask=attention_mask)
+        out = self.engine().forward(input_ids, want=("text_embeds", "last_hidden_state"))
+        pdt = next(self.parameters()).dtype
+        return SimpleNamespace(text_embeds=out["text_embeds"].to(pdt, copy=True), last_hidden_state=out["last_hidden_state"].to(pdt, copy=True))
+
+
+def style_image_tokens(encoder, image_proj, images, processor=None, neg_content_embeds=None, neg_content_scale=1.0):
     """(tokens, uncond_tokens), each [B, clip_extra_context_tokens, cross_attention_dim]: what the app computes from the style
     image (:392-409) -- processor(images).pixel_values -> encoder(...).image_embeds -> image_proj(embeds) and
     image_proj(zeros_like(embeds)) -- ready to be passed as c_ip in cond / un_cond.  images: a PIL image or a uint8 HWC
-    array, or a list of them.  processor: a CLIPImageProcessor (default: CLIPImageProcessor())."""
+    array, or a list of them.  processor: a CLIPImageProcessor (default: CLIPImageProcessor()).  neg_content_embeds: the
+    text_embeds of a negative content prompt (CLIPTextEncoder): neg_content_scale times them is taken off the image embeds
+    before image_proj (:401-403); the unconditional tokens are the same either way."""
     if processor is None:
         from transformers import CLIPImageProcessor
         processor = CLIPImageProcessor()
@@ -174,4 +267,6 @@ def style_image_tokens(encoder, image_proj, images, processor=None):
         embeds = encoder(pixel_values).image_embeds
         pdt = next(image_proj.parameters()).dtype
         embeds = embeds.to(device=next(image_proj.parameters()).device, dtype=pdt)
+        if neg_content_embeds is not None:
+            embeds = embeds - neg_content_scale * neg_content_embeds.to(device=embeds.device, dtype=pdt)
         return image_proj(embeds), image_proj(torch.zeros_like(embeds))

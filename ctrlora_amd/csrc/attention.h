@@ -67,11 +67,15 @@ extern int g_attn_variant;   // probe hook: 0 = heuristic, 1 = tile-synchronous 
 bool attn_fwd40_applies(const AttnFwdArgs& a);
 int attn_fwd40(const AttnFwdArgs& a, const void* V, long ldv, hipStream_t st);
 int attn_delta(const AttnBwdArgs& a, hipStream_t st);   // delta[q] = sum_d dO[q,d] O[q,d]  (bf16)
+// causal self-attention forward, d_head 64, N <= 128 (attention_causal.hip): Q / K / V / O row-major [B*N, ld], no LSE
+int attn_causal_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O, long ldo, int B, int H,
+                    int N, int dh, float scale, hipStream_t st);
 
 // Read-only record of what the last attention entry point launched (csrc/debug_hooks.h: cl_debug_attention_last_launch).
-// Host side only: every launcher of the four attention files fills it next to its hipLaunchKernelGGL; an entry point that
+// Host side only: every launcher of the attention files fills it next to its hipLaunchKernelGGL; an entry point that
 // refuses its arguments leaves kind = 0.  No kernel, launch or argument depends on it.
-enum { ATTN_FAM_TR = 1, ATTN_FAM_TR_IP = 2, ATTN_FAM_HYB = 3, ATTN_FAM_FWD40 = 4, ATTN_FAM_FOLD = 5, ATTN_FAM_TRANSPOSED = 6 };
+enum { ATTN_FAM_TR = 1, ATTN_FAM_TR_IP = 2, ATTN_FAM_HYB = 3, ATTN_FAM_FWD40 = 4, ATTN_FAM_FOLD = 5, ATTN_FAM_TRANSPOSED = 6,
+       ATTN_FAM_CAUSAL = 7 };
 enum { ATTN_BIT_TAIL = 1, ATTN_BIT_TQ = 2, ATTN_BIT_TK = 4, ATTN_BIT_PRIO = 8 };
 struct AttnLaunchRec {
   int kind;          // 0 nothing launched, 1 forward, 2 backward

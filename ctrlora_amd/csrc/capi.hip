@@ -303,6 +303,12 @@ int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long 
   return attn_fwd_ip(a, ip, dtype, S(stream));
 }
 
+int cl_attention_causal_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv, void* O,
+                            long ldo, int B, int H, int N, int dh, float scale, void* stream) {
+  attn_rec_begin();
+  return attn_causal_fwd(dtype, Q, ldq, K, ldk, V, ldv, O, ldo, B, H, N, dh, scale, S(stream));
+}
+
 int cl_attention_bwd_v2(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                         const void* O, long ldo, const void* dO, long lddo, const float* LSE, float* Delta,
                         int lse_stride, void* dQ, long lddq, void* dK, long lddk, void* dV, long lddv, int B, int H,
@@ -330,6 +336,8 @@ int cl_pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, 
 int cl_pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R, int C, int Cpad, void* stream) { return pack2d(dtype, in, ldi, out, ldo, R, C, Cpad, S(stream)); }
 int cl_vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S_, int P, int Kpad, void* stream) { return vit_patch_rows(dtype, pixels, out, ldo, B, C, S_, P, Kpad, S(stream)); }
 int cl_vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T, int D, void* stream) { return vit_tokens(dtype, patch, ldp, cls, pos, out, ldo, B, T, D, S(stream)); }
+int cl_clip_text_embed(int dtype, const long* ids, const float* tok, const float* pos, void* out, long ldo, int B, int T, int D, int vocab, void* stream) { return clip_text_embed(dtype, ids, tok, pos, out, ldo, B, T, D, vocab, S(stream)); }
+int cl_gather_rows(int dtype, const void* src, long lds_, const long* rows, void* dst, long ldd, int R, int D, int nsrc, void* stream) { return gather_rows(dtype, src, lds_, rows, dst, ldd, R, D, nsrc, S(stream)); }
 int cl_repack(int dtype, const float* flat, const long* desc, const int* tile_prefix, int ndesc, int total_tiles, void* stream) { return repack(dtype, flat, desc, tile_prefix, ndesc, total_tiles, S(stream)); }
 int cl_timestep_embedding(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, void* stream) { return timestep_embed(dtype, t, freqs, out, ldo, B, half, S(stream)); }
 int cl_qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac, float* out, int B, long per_sample, void* stream) { return qsample(z, noise, t, sqrt_ac, sqrt_1mac, out, B, per_sample, S(stream)); }

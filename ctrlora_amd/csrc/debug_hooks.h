@@ -14,7 +14,7 @@ int cl_debug_attention_variant(int variant);   /* also 21 = 0 with the dK/dV ker
 int cl_debug_attention_fuse_delta(int on);
 /* Read-only: what the last attention entry point of this process launched (csrc/attention.h: AttnLaunchRec; host side only, no
  * GPU touched).  out[0..15] = kind (0 nothing: the call was refused, 1 forward, 2 backward), family (1 tile-synchronous
- * transpose-free, 2 image-prompt, 3 hybrid, 4 pre-scaled d_head-40 forward, 5 fold backward, 6 transposed), dtype, d_head,
+ * transpose-free, 2 image-prompt, 3 hybrid, 4 pre-scaled d_head-40 forward, 5 fold backward, 6 transposed, 7 causal), dtype, d_head,
  * 64-row fragments per workgroup of the forward / dQ / dK-dV kernel (0 = did not run), bits (1 TAIL, 2 TQ, 4 TK template
  * forms, 8 s_setprio form), hybrid lookahead, workgroup remap, separate delta launch, dK/dV kernel ran, workgroups of the
  * forward / dQ / dK-dV kernel, tile length along the looped dimension.  CL_EINVAL for a null pointer. */

@@ -13,7 +13,8 @@ enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
-  EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS
+  EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
+  EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS
 };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
@@ -69,5 +70,9 @@ int pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R, in
 int vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, hipStream_t st);
 int vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
                int D, hipStream_t st);
+// CLIPTextEmbeddings: token rows gathered by id (clamped to [0, vocab)) + position embedding; rows gathered by index (clamped)
+int clip_text_embed(int dtype, const long* ids, const float* tok, const float* pos, void* out, long ldo, int B, int T, int D, int vocab,
+                    hipStream_t st);
+int gather_rows(int dtype, const void* src, long lds_, const long* rows, void* dst, long ldd, int R, int D, int nsrc, hipStream_t st);
 
 }  // namespace cl

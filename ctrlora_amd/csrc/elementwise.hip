@@ -627,6 +627,42 @@ __global__ void vit_tokens_kernel(const T* __restrict__ patch, long ldp, const f
   }
 }
 
+// CLIPTextEmbeddings: out[b T + t, :] = tok[ids[b, t]] + pos[t] (fp32 tables, fp32 add, one rounding to T).  An id outside
+// [0, vocab) is clamped: nothing is read out of range whatever the ids hold.
+template <typename T>
+__global__ void clip_text_embed_kernel(const long* __restrict__ ids, const float* __restrict__ tok, const float* __restrict__ pos,
+                                       T* __restrict__ out, long ldo, int B, int Tn, int D, int vocab) {
+  const int D8 = D / 8;
+  const long n = (long)B * Tn * D8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / D8; const int c = (int)(i - row * D8) * 8;
+    const int t = (int)(row % Tn);
+    long id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    float v[8], p[8];
+    load8(tok + id * D + c, v);
+    load8(pos + (long)t * D + c, p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += p[e];
+    store8(out + row * ldo + c, v);
+  }
+}
+// dst[r, :] = src[rows[r], :] (the pooled rows of CLIPTextTransformer); a row index outside [0, nsrc) is clamped
+template <typename T>
+__global__ void gather_rows_kernel(const T* __restrict__ src, long lds_, const long* __restrict__ rows, T* __restrict__ dst, long ldd,
+                                   int R, int D, int nsrc) {
+  const int D8 = D / 8;
+  const long n = (long)R * D8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / D8; const int c = (int)(i - r * D8) * 8;
+    long s = rows[r];
+    s = s < 0 ? 0 : (s >= nsrc ? nsrc - 1 : s);
+    float v[8];
+    load8(src + s * lds_ + c, v);
+    store8(dst + r * ldd + c, v);
+  }
+}
+
 // ================================================================= host launchers
 // Every launcher decides its refusals (CL_EINVAL; listed per entry point in include/ctrlora_hip.h) on the host before anything is
 // launched, and keeps a read-only record of what it launched (elementwise.h: EwLaunchRec): reset on entry, written by ew_done()
@@ -665,6 +701,27 @@ int vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const f
   if (dtype == CL_BF16) hipLaunchKernelGGL((vit_tokens_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)patch, ldp, cls, pos, (bf16_t*)out, ldo, B, T, D);
   else hipLaunchKernelGGL((vit_tokens_kernel<float>), grid, dim3(256), 0, st, (const float*)patch, ldp, cls, pos, (float*)out, ldo, B, T, D);
   return ew_done(EW_VIT_TOKENS, dtype, grid, 256);
+}
+int clip_text_embed(int dtype, const long* ids, const float* tok, const float* pos, void* out, long ldo, int B, int T, int D, int vocab,
+                    hipStream_t st) {
+  ew_rec_begin();
+  if (bad_dtype(dtype) || !ids || !tok || !pos || !out) return CL_EINVAL;
+  if (B < 1 || T < 1 || vocab < 1 || D < 8 || D % 8 || ldo % 8 || ldo < D) return CL_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(ids) & 7) || mis16(tok) || mis16(pos) || mis16(out)) return CL_EINVAL;
+  const dim3 grid(ew_grid((long)B * T * (D / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((clip_text_embed_kernel<bf16_t>), grid, dim3(256), 0, st, ids, tok, pos, (bf16_t*)out, ldo, B, T, D, vocab);
+  else hipLaunchKernelGGL((clip_text_embed_kernel<float>), grid, dim3(256), 0, st, ids, tok, pos, (float*)out, ldo, B, T, D, vocab);
+  return ew_done(EW_CLIP_TEXT_EMBED, dtype, grid, 256);
+}
+int gather_rows(int dtype, const void* src, long lds_, const long* rows, void* dst, long ldd, int R, int D, int nsrc, hipStream_t st) {
+  ew_rec_begin();
+  if (bad_dtype(dtype) || !src || !rows || !dst) return CL_EINVAL;
+  if (R < 1 || nsrc < 1 || D < 8 || D % 8 || lds_ % 8 || ldd % 8 || lds_ < D || ldd < D) return CL_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(rows) & 7) || mis16(src) || mis16(dst)) return CL_EINVAL;
+  const dim3 grid(ew_grid((long)R * (D / 8)));
+  if (dtype == CL_BF16) hipLaunchKernelGGL((gather_rows_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)src, lds_, rows, (bf16_t*)dst, ldd, R, D, nsrc);
+  else hipLaunchKernelGGL((gather_rows_kernel<float>), grid, dim3(256), 0, st, (const float*)src, lds_, rows, (float*)dst, ldd, R, D, nsrc);
+  return ew_done(EW_GATHER_ROWS, dtype, grid, 256);
 }
 int geglu_fwd(int dtype, const void* h, long ldh, void* out, long ldo, long M, int F, hipStream_t st) {
   ew_rec_begin();

@@ -88,6 +88,7 @@ _SIGS = {
     "cl_attention_fwd_ip": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P],
     "cl_attention_bwd_v2": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _I, _P, _L, _P, _L, _P, _L,
                             _I, _I, _I, _I, _I, _F, _I, _P, _P],
+    "cl_attention_causal_fwd": [_I, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
     "cl_geglu_fwd": [_I, _P, _L, _P, _L, _L, _I, _P],
     "cl_geglu_bwd": [_I, _P, _L, _P, _L, _P, _L, _L, _I, _P],
     "cl_silu_fwd": [_I, _P, _P, _L, _P],
@@ -101,6 +102,8 @@ _SIGS = {
     "cl_pack2d": [_I, _P, _L, _P, _L, _L, _I, _I, _P],
     "cl_vit_patch_rows": [_I, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "cl_vit_tokens": [_I, _P, _L, _P, _P, _P, _L, _I, _I, _I, _P],
+    "cl_clip_text_embed": [_I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "cl_gather_rows": [_I, _P, _L, _P, _P, _L, _I, _I, _I, _P],
     "cl_repack": [_I, _P, _P, _P, _I, _I, _P],
     "cl_timestep_embedding": [_I, _P, _P, _P, _L, _I, _I, _P],
     "cl_qsample": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
@@ -528,6 +531,15 @@ def attention(q, k, v, o, lse, B, H, N, Nkv, dh, scale, *, q_prescaled=False, ip
     return attention_fwd_ip(q, k, vt, k_ip, vt_ip, o, B, H, N, Nkv, Nip, dh, scale, ip_scale)
 
 
+def attention_causal(q, k, v, o, B, H, N, dh, scale):
+    """o[b, i] = softmax_{j <= i}(scale q_i k_j) v_j per head: causal self-attention, q / k / v / o [B*N, >= H*dh] row-major, d_head 64,
+    N <= 128, bf16 or fp32 (cl_attention_causal_fwd, csrc/attention_causal.hip)."""
+    assert dt(q) == dt(k) == dt(v) == dt(o)
+    _chk(lib().cl_attention_causal_fwd(dt(q), q.data_ptr(), ld(q), k.data_ptr(), ld(k), v.data_ptr(), ld(v), o.data_ptr(), ld(o),
+                                       B, H, N, dh, float(scale), stream()), "cl_attention_causal_fwd")
+    return o
+
+
 def attention_backward(q, k, v, o, do, lse, delta, dq, dk, dv, B, H, N, Nkv, dh, scale, *, q_prescaled=False):
     """dq, dk, dv (dk / dv may be None) of attention(); lse as the forward wrote it, delta a scratch of lse's shape."""
     if dt(q) == BF16:
@@ -625,6 +637,32 @@ def vit_patch_rows(pixels, out, P):
     _chk(lib().cl_vit_patch_rows(dt(out), pixels.data_ptr(), out.data_ptr(), ld(out), B, C_, S, P, out.shape[1], stream()),
          "cl_vit_patch_rows")
     return out
+
+
+def clip_text_embed(ids, tok, pos, out):
+    """out[b T + t] = tok[ids[b, t]] + pos[t] (ids [B, T] int64, tok [vocab, D] / pos [>= T, D] fp32): cl_clip_text_embed.  The
+    kernel clamps an id outside [0, vocab); ids that come from the host are checked here, where that costs no sync."""
+    B, T = ids.shape
+    vocab, D = tok.shape
+    assert ids.dtype == torch.long and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
+    assert out.shape == (B * T, D) and pos.shape[0] >= T and pos.shape[1] == D and tok.dtype == pos.dtype == torch.float32
+    if not ids.is_cuda:
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= vocab):
+            raise HipError(f"cl_clip_text_embed: token id outside [0, {vocab})")
+        ids = ids.to(out.device)
+    _chk(lib().cl_clip_text_embed(dt(out), ids.data_ptr(), tok.data_ptr(), pos.data_ptr(), out.data_ptr(), ld(out), B, T, D, vocab,
+                                  stream()), "cl_clip_text_embed")
+    return out
+
+
+def gather_rows(src, rows, dst):
+    """dst[r] = src[rows[r]] (rows int64 on the device, clamped to src's rows): cl_gather_rows."""
+    R, D = dst.shape
+    assert rows.dtype == torch.long and rows.is_cuda and rows.is_contiguous() and rows.numel() == R and src.shape[1] == D
+    assert src.dtype == dst.dtype
+    _chk(lib().cl_gather_rows(dt(dst), src.data_ptr(), ld(src), rows.data_ptr(), dst.data_ptr(), ld(dst), R, D, src.shape[0], stream()),
+         "cl_gather_rows")
+    return dst
 
 
 def vit_tokens(patch, cls, pos, out, B):

@@ -308,6 +308,14 @@ int cl_attention_bwd_v2(int dtype, const void* Q, long ldq, const void* K, long 
 int cl_attention_fwd_ip(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                         const void* Kip, long ldkip, const void* Vip, long ldvip, void* O, long ldo, int B, int H,
                         int N, int Nkv, int Nip, int dh, float scale, float ip_scale, int flags, void* stream);
+/* Causal self-attention forward (CLIPTextTransformer: the causal mask of modeling_clip.py added to CLIPAttention's scores),
+ * added in ABI 7 (compatible):   O[b, i, h] = softmax_{j <= i}(scale q_i . k_j) v_j,   N queries = N keys, no LSE.
+ * Q / K / V / O are row-major [B*N, ld] with head h at columns [h*dh, (h+1)*dh), as in cl_attention_fwd_v2; bf16 or fp32.
+ * fp32 scores and softmax; the unnormalised P is rounded to `dtype` before P.V, O once on the store.  CL_EINVAL, nothing
+ * launched, for dh != 64, N < 1 or N > 128, a row pitch that is not a multiple of 16 bytes or is narrower than H*dh, a
+ * null or not 16-byte aligned pointer. */
+int cl_attention_causal_fwd(int dtype, const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
+                            void* O, long ldo, int B, int H, int N, int dh, float scale, void* stream);
 /* row_ws (ABI 6; may be NULL): scratch of B * H * lse_stride * 32 bytes, 16-byte aligned.  With CL_ATTN_Q_PRESCALED and
  * d_head 40 the backward kernels keep (-lse, -delta) of every query row there as bf16 triples and feed them through spare
  * contraction slots of the matrix products, which then deliver s - lse and dP - delta (attention.py:171-192's backward with
@@ -353,6 +361,14 @@ int cl_pack2d(int dtype, const float* in, long ldi, void* out, long ldo, long R,
 int cl_vit_patch_rows(int dtype, const float* pixels, void* out, long ldo, int B, int C, int S, int P, int Kpad, void* stream);
 int cl_vit_tokens(int dtype, const void* patch, long ldp, const float* cls, const float* pos, void* out, long ldo, int B, int T,
                   int D, void* stream);
+/* CLIPTextEmbeddings.forward (modeling_clip.py: token_embedding(input_ids) + position_embedding), added in ABI 7 (compatible):
+ * out[b T + t, :] = tok[ids[b, t], :] + pos[t, :]; ids [B, T] int64, tok [vocab, D] and pos [>= T, D] fp32, out in `dtype`, the
+ * add in fp32, one rounding.  D % 8 == 0.  An id outside [0, vocab) is clamped in the kernel: it never reads out of range.
+ * cl_gather_rows: dst[r, :] = src[rows[r], :] for r < R (the pooled end-of-text rows); rows int64 on the device, an index
+ * outside [0, nsrc) clamped.  D % 8 == 0, pitches multiples of 8 elements, pointers 16-byte aligned (ids / rows 8-byte). */
+int cl_clip_text_embed(int dtype, const long* ids, const float* tok, const float* pos, void* out, long ldo, int B, int T, int D,
+                       int vocab, void* stream);
+int cl_gather_rows(int dtype, const void* src, long lds, const long* rows, void* dst, long ldd, int R, int D, int nsrc, void* stream);
 /* One-launch refresh of the engine's storage-dtype copies of all trainable matrices from the flat fp32
  * master buffer after an optimizer step.  desc = device table of 8 longs per matrix {src offset in floats,
  * rows << 32 | cols, dst [rows][cols] or 0, dst^T [cols][rows] or 0, source row stride (0 = cols), dst row stride

@@ -1,8 +1,8 @@
 """FrozenCLIPEmbedder (API of ldm/modules/encoders/modules.py:88-131).
 
-The frozen CLIP ViT-L/14 text encoder is outside the hand-written path (about 1 % of the FLOPs,
-SURVEY.md 2.1 row 14); it runs through HF transformers.  There is no network in the build / bench environment, so
-construction never downloads; benchmarks feed a synthetic (B,77,768) context.
+The frozen CLIP ViT-L/14 text encoder (about 1 % of the FLOPs) is an HF transformers module tree; on a
+GPU its forward runs on the HIP engine (ctrlora_amd/engine/clip_text.py), elsewhere through HF.  There is no network in the
+build / bench environment, so construction never downloads; benchmarks feed a synthetic (B,77,768) context.
 """
 import torch
 import torch.nn as nn
@@ -29,7 +29,12 @@ class FrozenCLIPEmbedder(AbstractEncoder):
     """CLIP ViT-L/14 text encoder through HF transformers (ldm/modules/encoders/modules.py:88-131).  The module tree
     (`transformer.text_model.*`, the keys an SD checkpoint carries under `cond_stage_model.`) is built from the model's
     CONFIG -- no download; pretrained weights are picked up from a local HF cache when one exists, otherwise they come
-    from the SD checkpoint the scripts load.  The tokenizer needs its vocabulary files locally."""
+    from the SD checkpoint the scripts load.  The tokenizer needs its vocabulary files locally.
+
+    On a GPU, with a config the executor covers (ctrlora_amd/engine/clip_text.py: check_config), forward runs on the HIP engine
+    in `engine_dtype` -- fp32 unless set_engine_dtype(torch.bfloat16): the reference runs this encoder in fp32, and the fp32
+    engine stays at about 1e-6 of the HF module's output.  use_engine = False (or the CPU, or another config) is the plain HF
+    module.  The engine's `forwards` counter says which path ran."""
     LAYERS = ["last", "pooled", "hidden"]
 
     def __init__(self, version="openai/clip-vit-large-patch14", device="cuda", max_length=77, freeze=True, layer="last",
@@ -54,8 +59,46 @@ class FrozenCLIPEmbedder(AbstractEncoder):
         self.tokenizer = None
         if layer == "hidden":
             assert layer_idx is not None and 0 <= abs(layer_idx) <= 12
+        self.engine_dtype = torch.float32
+        self.use_engine = True
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
         if freeze:
             self.freeze()
+
+    def set_engine_dtype(self, dtype):
+        self.engine_dtype = dtype
+        self.invalidate_engine()
+
+    def invalidate_engine(self):
+        self.__dict__.pop("_txt", None)
+
+    def _refresh_engine(self):
+        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
+        ex = self.__dict__.get("_txt")
+        if ex is not None:
+            if ex.device != next(self.transformer.parameters()).device:
+                self.invalidate_engine()
+            else:
+                ex.load(self.transformer.state_dict())
+
+    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
+        self.invalidate_engine()
+        return super()._apply(fn, *args, **kwargs)
+
+    def engine(self):
+        ex = self.__dict__.get("_txt")
+        if ex is None:
+            from ctrlora_amd.engine.clip_text import ClipTextE
+            ex = ClipTextE(self.transformer.state_dict(), self.transformer.config, self.engine_dtype,
+                           next(self.transformer.parameters()).device)
+            self.__dict__["_txt"] = ex
+        return ex
+
+    def _on_engine(self, ids):
+        from ctrlora_amd.engine.clip_text import supported
+        cfg = self.transformer.config
+        return (self.use_engine and next(self.transformer.parameters()).is_cuda and supported(cfg)
+                and 1 <= ids.shape[1] <= cfg.max_position_embeddings)
 
     def freeze(self):
         self.transformer = self.transformer.eval()
@@ -83,8 +126,13 @@ class FrozenCLIPEmbedder(AbstractEncoder):
     def forward(self, text):
         if isinstance(text, str):
             text = [text]
-        dev = next(self.transformer.parameters()).device
-        out = self.transformer(input_ids=self._tokens(text).to(dev), output_hidden_states=self.layer == "hidden")
+        p = next(self.transformer.parameters())
+        dev, ids = p.device, self._tokens(text)
+        if self._on_engine(ids):                # a fresh tensor of the HF path's shape and dtype: the buffers are the executor's
+            name = {"last": "last_hidden_state", "pooled": "pooler_output", "hidden": "hidden_state"}[self.layer]
+            out = self.engine().forward(ids, want=(name,), hidden_idx=self.layer_idx)[name].to(p.dtype, copy=True)
+            return out[:, None, :] if self.layer == "pooled" else out
+        out = self.transformer(input_ids=ids.to(dev), output_hidden_states=self.layer == "hidden")
         if self.layer == "last":
             return out.last_hidden_state
         if self.layer == "pooled":
