@@ -212,8 +212,59 @@ class ControlLDM(LatentDiffusion):
         return eng.forward(x_noisy, t, cond_txt, hints, control_scales=list(self.control_scales), lora_weights=weights,
                            only_mid_control=self.only_mid_control, context_ip=context_ip)
 
+    def _posterior_draws(self, mom_x, mom_h):
+        """z = scale_factor * (mean + std * e) for the cached posteriors of the target and of the condition (CPU fp32
+        [B, 2C, h, w], mean | std).  e_x, then e_h, are torch.randn draws on the CPU generator: the reference's posterior draws,
+        in the order the live path takes them.  On the GPU the moments and the draws go through pinned staging buffers, one
+        non-blocking copy each on the current stream, and one launch of the pair kernel forms both latents."""
+        B, C2, h, w = mom_x.shape
+        shape = (B, C2 // 2, h, w)
+        dev = self.device
+        if dev.type != "cuda":
+            outs = []
+            for mom in (mom_x, mom_h):                     # target first, hint second
+                mean, std = torch.chunk(mom.float(), 2, dim=1)
+                outs.append(self.scale_factor * (mean + std * torch.randn(shape)))
+            return outs[0], outs[1]
+        from ctrlora_amd import hip
+        if torch.cuda.is_current_stream_capturing():
+            # the draws are host work (the reference's CPU generator) and the staging buffers are recycled under a host wait:
+            # captured, one batch and one pair of draws would be baked into the graph and replayed for ever
+            raise RuntimeError("a batch of cached posteriors cannot be turned into latents inside a hipGraph capture: call "
+                               "get_input outside the captured region and hand the step its z and hint latent")
+        stages = self.__dict__.setdefault("_posterior_stages", {})     # one set per batch shape (training batch, log_images' N)
+        st = stages.get(tuple(mom_x.shape))
+        if st is None:
+            st = stages[tuple(mom_x.shape)] = dict(
+                mom=[torch.empty(mom_x.shape, dtype=torch.float32).pin_memory() for _ in range(2)],
+                e=[torch.empty(shape, dtype=torch.float32).pin_memory() for _ in range(2)], done=torch.cuda.Event())
+        else:
+            st["done"].synchronize()                       # this shape's previous copies have left the staging buffers
+        for dst, src in zip(st["mom"], (mom_x, mom_h)):
+            dst.copy_(src)
+        for e in st["e"]:                                  # target first, hint second
+            torch.randn(shape, out=e)
+        d_mom = [t.to(dev, non_blocking=True) for t in st["mom"]]
+        d_e = [t.to(dev, non_blocking=True) for t in st["e"]]
+        st["done"].record()
+        z, hint_z = torch.empty(shape, device=dev), torch.empty(shape, device=dev)
+        hip.posterior_sample_pair(d_mom[0], d_e[0], z, self.scale_factor, d_mom[1], d_e[1], hint_z)
+        return z, hint_z
+
     @torch.no_grad()
     def get_input(self, batch, k, bs=None, *args, **kwargs):
+        if "jpg_moments" in batch:
+            # a batch of datasets.cached_latents.CachedLatentDataset: the stored posteriors stand in for both VAE encodes and no
+            # image key is read.  The live path draws e_x here and e_h later, inside apply_model (_hint_latent), both from the
+            # CPU generator; nothing between the two touches that generator -- the text encoder draws nothing, t and the
+            # q_sample noise come from the device generator -- so drawing e_h right after e_x gives the same numbers, and
+            # with the pair kernel's roundings the same latents bit for bit.
+            mom_x, mom_h = torch.as_tensor(batch["jpg_moments"]), torch.as_tensor(batch["hint_moments"])
+            xc = batch[self.cond_stage_key]
+            if bs is not None:
+                mom_x, mom_h, xc = mom_x[:bs], mom_h[:bs], xc[:bs]
+            z, hint_z = self._posterior_draws(mom_x.contiguous(), mom_h.contiguous())
+            return z, dict(c_crossattn=[self.get_learned_conditioning(xc)], c_concat=[hint_z])
         x, c = super().get_input(batch, self.first_stage_key, *args, **kwargs)
         control = batch[self.control_key]
         if bs is not None:
@@ -236,7 +287,9 @@ class ControlLDM(LatentDiffusion):
         N = min(z.shape[0], N)
         c_cat, c_txt = c["c_concat"][0][:N], c["c_crossattn"][0][:N]
         extra = {k: v for k, v in c.items() if k not in ("c_concat", "c_crossattn")}      # 'task' when pre-training
-        log = {"reconstruction": self.decode_first_stage(z[:N]), "control": c_cat * 2.0 - 1.0,
+        # a cached batch (get_input) has no condition image: its hint latent is decoded for the grid, and conditions the samples
+        control = self.decode_first_stage(c_cat) if "jpg_moments" in batch else c_cat * 2.0 - 1.0
+        log = {"reconstruction": self.decode_first_stage(z[:N]), "control": control,
                "conditioning": log_txt_as_img((512, 512), list(batch[self.cond_stage_key])[:N], size=16)}
         cond = dict(c_concat=[c_cat], c_crossattn=[c_txt], **extra)
         if sample:

@@ -197,6 +197,40 @@ __global__ void qsample_kernel(const float* __restrict__ z, const float* __restr
     out[i] = a + b;
   }
 }
+// ---------------------------------------------------------------- posterior sample (ddpm.py:655-662, distributions.py:35-37)
+// out = scale * (mean + std * e) for one or two tensors in ONE launch: mom = [B][2 per] (mean | std), e / out = [B][per], fp32.
+// work items [0, nw) belong to tensor a, [nw, 2 nw) to tensor b; W = elements per work item (4: 16-byte loads and stores, 1: scalar)
+template <int W>
+__global__ void posterior_sample_pair_kernel(const float* __restrict__ mom_a, const float* __restrict__ e_a, float* __restrict__ out_a,
+                                             const float* __restrict__ mom_b, const float* __restrict__ e_b, float* __restrict__ out_b,
+                                             long per, long nw, int ntensors, float scale) {
+  // a rounded product, a rounded sum, a rounded product, as torch evaluates scale_factor * (mean + std * randn): a contracted
+  // std * e + mean is an FMA and differs from DiagonalGaussianDistribution.sample in the last bit of some elements
+#pragma clang fp contract(off)
+  const long perw = per / W, total = nw * ntensors;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const bool second = i >= nw;
+    const long w = second ? i - nw : i;
+    const float* mom = second ? mom_b : mom_a;
+    const float* e = second ? e_b : e_a;
+    float* out = second ? out_b : out_a;
+    const long b = w / perw, j = (w - b * perw) * W;
+    const float* mean = mom + b * 2 * per + j;
+    if constexpr (W == 4) {
+      const float4 m = *reinterpret_cast<const float4*>(mean), s = *reinterpret_cast<const float4*>(mean + per);
+      const float4 n = *reinterpret_cast<const float4*>(e + w * 4);
+      float4 p, z, o;
+      p.x = s.x * n.x; p.y = s.y * n.y; p.z = s.z * n.z; p.w = s.w * n.w;
+      z.x = m.x + p.x; z.y = m.y + p.y; z.z = m.z + p.z; z.w = m.w + p.w;
+      o.x = scale * z.x; o.y = scale * z.y; o.z = scale * z.z; o.w = scale * z.w;
+      *reinterpret_cast<float4*>(out + w * 4) = o;
+    } else {
+      const float p = mean[per] * e[w];
+      const float z = mean[0] + p;
+      out[w] = scale * z;
+    }
+  }
+}
 // loss += sum((eps - target)^2) / n ; d_eps = 2 (eps - target) / n * gscale
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ eps, const float* __restrict__ target,
                                                   float* __restrict__ d_eps, float* __restrict__ loss, long n,
@@ -835,6 +869,21 @@ int qsample(const float* z, const float* noise, const long* t, const float* sqrt
   const dim3 grid(ew_grid(n));
   hipLaunchKernelGGL(qsample_kernel, grid, dim3(256), 0, st, z, noise, t, sqrt_ac, sqrt_1mac, out, per, n);
   return ew_done(EW_QSAMPLE, -1, grid, 256);
+}
+int posterior_sample_pair(const float* mom_a, const float* e_a, float* out_a, const float* mom_b, const float* e_b, float* out_b,
+                          int B, long per, float scale, hipStream_t st) {
+  ew_rec_begin();
+  if (B < 1 || per < 1 || !mom_a || !e_a || !out_a) return CL_EINVAL;
+  const int given_b = (mom_b ? 1 : 0) + (e_b ? 1 : 0) + (out_b ? 1 : 0);
+  if (given_b != 0 && given_b != 3) return CL_EINVAL;              // a half-given second tensor
+  const int nt = given_b ? 2 : 1;
+  const bool vec = per % 4 == 0 && !mis16(mom_a) && !mis16(e_a) && !mis16(out_a) &&
+                   (!given_b || (!mis16(mom_b) && !mis16(e_b) && !mis16(out_b)));
+  const long nw = (long)B * (vec ? per / 4 : per);
+  const dim3 grid(ew_grid(nw * nt));
+  if (vec) hipLaunchKernelGGL((posterior_sample_pair_kernel<4>), grid, dim3(256), 0, st, mom_a, e_a, out_a, mom_b, e_b, out_b, per, nw, nt, scale);
+  else hipLaunchKernelGGL((posterior_sample_pair_kernel<1>), grid, dim3(256), 0, st, mom_a, e_a, out_a, mom_b, e_b, out_b, per, nw, nt, scale);
+  return ew_done(EW_POSTERIOR_PAIR, -1, grid, 256, vec ? 1 : 0, nt);
 }
 int mse_loss(const float* eps, const float* target, float* d_eps, float* loss, long n, float gscale, hipStream_t st) {
   ew_rec_begin();

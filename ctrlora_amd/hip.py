@@ -122,6 +122,7 @@ _SIGS = {
     "cl_dpmpp_step": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _L, _P],
     "cl_dpmpp_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
     "cl_dpm_set_t": [_P, _P, _I, _P, _I, _P],
+    "cl_posterior_sample_pair": [_P, _P, _P, _P, _P, _P, _I, _L, _F, _P],
 }
 EXPORTED = tuple(_SIGS.keys())
 # probe hooks (ctrlora_amd/csrc/debug_hooks.h): exported by the library, not part of include/ctrlora_hip.h
@@ -371,8 +372,23 @@ def gemm(a1, w1, out, *, a2=None, w2=None, bias=None, rowbias=None, rows_per_bat
     return out
 
 
+# Opt-in (CTRLORA_WGRAD_F32_DETERMINISTIC=1; off by default, and then nothing below changes): the weight gradients of the fp32
+# parity mode as a pure function of their operands.  cl_weight_grad splits K and accumulates with fp32 atomics, so the last bits of
+# an fp32 step's gradients depend on the order in which the workgroups arrive; with the switch on, the same product goes through
+# cl_gemm with dW as its own residual (dW = scale * product + dW), where the launcher splits K through the workspace and sums the
+# slabs in a fixed order.  Another launch form and another summation order than the default's: for comparisons that need bits.
+WGRAD_F32_DETERMINISTIC = os.environ.get("CTRLORA_WGRAD_F32_DETERMINISTIC", "0") == "1"
+
+
 def weight_grad(dyT, xT, dW, scale=1.0):
     """dW[N,K] (fp32) += scale * dyT[N,Mp] . xT[K,Mp]^T  (split-K, fp32 atomics)."""
+    if WGRAD_F32_DETERMINISTIC and dyT.dtype == torch.float32:
+        # the epilogue reads and writes dW eight columns (two 16-byte vectors) at a time
+        if dW.data_ptr() % 16 or ld(dW) % 8 or dW.shape[1] % 8:
+            raise HipError(f"deterministic fp32 weight gradient: dW must be 16-byte aligned with a row stride and a width that are "
+                           f"multiples of 8 (got offset {dW.data_ptr() % 16}, ld {ld(dW)}, width {dW.shape[1]})")
+        gemm(dyT, xT, dW, residual=dW, alpha=scale, beta=1.0, out_f32=True)
+        return
     _chk(lib().cl_weight_grad(dt(dyT), dyT.data_ptr(), ld(dyT), xT.data_ptr(), ld(xT), dW.data_ptr(), ld(dW),
                               dyT.shape[0], xT.shape[0], dyT.shape[1], scale, stream()), "cl_weight_grad")
 
@@ -693,6 +709,20 @@ def qsample(z, noise, t, sqrt_ac, sqrt_1mac, out):
     _chk(lib().cl_qsample(z.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
                           out.data_ptr(), B, z.numel() // B, stream()), "cl_qsample")
     return out
+
+
+def posterior_sample_pair(mom_a, e_a, out_a, scale, mom_b=None, e_b=None, out_b=None):
+    """out = scale * (mean + std * e) for one posterior, or two of the same shape, in one launch (fp32, contiguous):
+    mom = [B, 2C, h, w] (mean | std), e / out = [B, C, h, w].  Bit-identical to the three torch fp32 ops."""
+    ts = [t for t in (mom_a, e_a, out_a, mom_b, e_b, out_b) if t is not None]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in ts)
+    B = e_a.shape[0]
+    per = e_a.numel() // B if B else 0          # an empty batch is the kernel's refusal (B < 1), not a division here
+    assert mom_a.numel() == 2 * e_a.numel() == 2 * out_a.numel()
+    assert mom_b is None or (mom_b.numel() == mom_a.numel() and e_b.numel() == e_a.numel() and out_b.numel() == out_a.numel())
+    _chk(lib().cl_posterior_sample_pair(mom_a.data_ptr(), e_a.data_ptr(), out_a.data_ptr(), ptr(mom_b), ptr(e_b), ptr(out_b),
+                                        B, per, float(scale), stream()), "cl_posterior_sample_pair")
+    return out_a, out_b
 
 
 def mse_loss(eps, target, d_eps, loss, gscale=1.0):

@@ -404,6 +404,14 @@ int cl_softmax_rows(int dtype, const float* S, long lds, void* P, long ldp, long
 /* DDPM.q_sample (ddpm.py:356-359): out = sqrt_ac[t_b] * z + sqrt_1mac[t_b] * noise */
 int cl_qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
                float* out, int B, long per_sample, void* stream);
+/* LatentDiffusion.get_first_stage_encoding on a stored posterior (ddpm.py:655-662, distributions.py:35-37), added in ABI 7
+ * (compatible): out = scale * (mean + std * e), fp32, for one tensor or for two of the same shape in ONE launch (target and
+ * condition of a training batch).  mom_* = [B][2 per_sample] (mean, then std, of each sample); e_* and out_* = [B][per_sample].
+ * A rounded product, a rounded sum, a rounded product, no FMA: the bits of the three torch fp32 ops.  16-byte loads and stores
+ * where per_sample % 4 == 0 and every pointer is 16-byte aligned, scalar otherwise.  No host synchronisation, no allocation.
+ * Refused: a null mom_a / e_a / out_a, B < 1, per_sample < 1, a second tensor given in part (mom_b, e_b, out_b: all or none). */
+int cl_posterior_sample_pair(const float* mom_a, const float* e_a, float* out_a, const float* mom_b, const float* e_b,
+                             float* out_b, int B, long per_sample, float scale, void* stream);
 /* p_losses MSE (ddpm.py:902-918): *loss = mean((eps - target)^2); d_eps = 2 (eps - target) / n * gscale */
 int cl_mse_loss(const float* eps, const float* target, float* d_eps, float* loss, long n, float gscale, void* stream);
 /* LatentDiffusion.p_losses' reduction, deterministic (ddpm.py:902-918, eps-parameterisation, logvar == 0):

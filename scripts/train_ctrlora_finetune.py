@@ -45,6 +45,9 @@ def get_parser():
     p.add_argument("--num_workers", type=int, default=None,
                    help="DataLoader worker processes (default: the reference's 16, capped at the host's cores); every epoch "
                         "forks them again, which is slow from a process with a large address space")
+    p.add_argument("--latent_cache", type=str, default=None,
+                   help="directory written by scripts/tool_cache_latents.py for this dataroot: train from the stored first-stage "
+                        "posteriors, so that no step runs the VAE encoder (CustomDataset only; off by default)")
     return p
 
 
@@ -76,7 +79,14 @@ def init_weights(model, sd_weights: dict, control_weights: dict, report_dir: str
 
 def build_dataloader(args, world_size: int, rank: int):
     from torch.utils.data import DataLoader, DistributedSampler, Subset
-    if args.multigen20m:
+    cache = getattr(args, "latent_cache", None)
+    if cache and args.multigen20m:
+        raise ValueError("--latent_cache cannot be combined with --multigen20m: MultiGen20M crops at random, so its images "
+                         "differ from epoch to epoch and their posteriors cannot be stored")
+    if cache:
+        from datasets.cached_latents import CachedLatentDataset
+        dataset = CachedLatentDataset(args.dataroot, cache, drop_rate=args.drop_rate)
+    elif args.multigen20m:
         from datasets.multigen20m import MultiGen20M
         dataset = MultiGen20M(path_json=os.path.join(args.dataroot, "json_files", f"aesthetics_plus_all_group_{args.task}_all.json"),
                               path_meta=args.dataroot, task=args.task, drop_rate=args.drop_rate)
@@ -113,6 +123,12 @@ def main(argv=None):
     init_weights(model, load_state_dict(args.sd_ckpt, location="cpu"), load_state_dict(args.cn_ckpt, location="cpu"))
     print(f"Successfully initialize SD from {args.sd_ckpt}")
     print(f"Successfully initialize ControlNet from {args.cn_ckpt}")
+    if args.latent_cache:
+        from ctrlora_amd import latent_cache
+        import torch
+        latent_cache.check_model(latent_cache.load_meta(args.latent_cache), model,
+                                 torch.float32 if str(args.precision) in ("32", "32-true") else torch.bfloat16)
+        print(f"Training from the latent cache {args.latent_cache}: the first stage encodes nothing")
     gc.collect()
     name = args.name or datetime.datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
     trainer = Trainer(max_steps=args.max_steps, accumulate_grad_batches=args.gradacc, precision=args.precision,
