@@ -74,12 +74,13 @@ class ControlFinetuneLDM(ControlLDM):
         return self._run(x_noisy, t, cond_txt, [self._hint_latent(cond)])
 
     @torch.no_grad()
-    def engine_train_step(self, x_start, cond, t, noise):
+    def engine_train_step(self, x_start, cond, t, noise, grad_scale=1.0):
         """p_losses (ddpm.py:885-920) + backward of the loss WITHOUT torch.autograd: q_sample, apply_model with
         recording, the p_losses reduction with d loss / d eps, the hand-written backward -- every launch is one of
         this library's kernels, so the whole thing is capturable as a hipGraph with no ATen nodes
         (ctrlora_amd.train.GraphedTrainStep).  Returns the device 3-vector {loss_simple, loss_vlb, loss}; gradients
-        land in the flat buffer the optimizer's parameters view."""
+        land in the flat buffer the optimizer's parameters view.  `grad_scale` multiplies d loss / d eps (not the three
+        returned scalars): 1 / accumulate_grad_batches under gradient accumulation, what `(loss / acc).backward()` does."""
         from ctrlora_amd import hip
         if self.loss_type != "l2" or self.original_elbo_weight != 0.:
             raise NotImplementedError("engine_train_step: l2 loss without the elbo term (every CtrLoRA config)")
@@ -95,7 +96,7 @@ class ControlFinetuneLDM(ControlLDM):
         scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
         d_eps = torch.empty_like(eps)
         hip.p_losses_mse(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
-                         1.0, float(self.l_simple_weight), 0.0)
+                         float(grad_scale), float(self.l_simple_weight), 0.0)
         eng.backward(d_eps)
         if self.dp is not None:
             self.dp.on_backward_done()

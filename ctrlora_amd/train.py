@@ -328,10 +328,23 @@ class GraphedTrainStep:
     structure on one rank (tests); "two" = the old A | all-reduce | B form; False = one graph.
     `model` is a ControlFinetuneLDM-like module (engine_train_step or p_losses / dp / control_model), `opt` its
     FusedAdamW.
+
+    A training loop (ctrlora_amd.trainer.Trainer) must not spend batches on warm-up, and under gradient accumulation one
+    optimizer step is several forward + backward passes.  For that:
+
+      * `warmup=0, capture=False` builds the object without running or capturing anything; `eager(...)` then runs one
+        micro-step with ordinary launches on the same direct path (each on its own batch), and `capture()` records the
+        graphs once the allocations are warm.
+      * `accumulate=True` captures the step as three pieces in every mode -- Z = zero_grad, F = forward + backward ADDING to
+        the gradient buffer (one graph, or the segments), B = AdamW + re-pack -- and `micro(..., first=, last=)` replays
+        [Z] F [B]: the first micro-step of an optimizer step clears, only the last one exchanges and optimizes.
+      * `grad_scale` multiplies d loss / d eps in every pass (1 / accumulate_grad_batches); it is a by-value kernel
+        argument, constant for a run, so it is baked into the capture.
     """
 
     def __init__(self, model, opt, z, cond_txt, hint, t, noise, warmup: int = 2, split_graphs=None,
-                 bucket_bytes: int = 32 << 20, reduce_fn=None, capture_error_mode=None):
+                 bucket_bytes: int = 32 << 20, reduce_fn=None, capture_error_mode=None, grad_scale: float = 1.0,
+                 accumulate: bool = False, capture: bool = True):
         import torch.distributed as dist
         self.model, self.opt = model, opt
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -366,41 +379,98 @@ class GraphedTrainStep:
                 return None
         self._reduce_fn = reduce_fn
 
-        direct = getattr(model, "engine_train_step", None)
-
-        def fwd_bwd():
-            opt.zero_grad()
-            cond = {"c_crossattn": [self.s_ctx], "c_concat": [self.s_hint]}
-            if direct is not None:
-                # p_losses + backward without autograd: the captured region holds hand-written kernel nodes only
-                # (no ATen launch, no memset node); out = {loss_simple, loss_vlb, loss}
-                self.loss3 = direct(self.s_z, cond, self.s_t, self.s_noise)
-                return self.loss3[2]
-            loss, _ = model.p_losses(self.s_z, cond, self.s_t, noise=self.s_noise)
-            loss.backward()
-            return loss.detach()
-
-        def reduce_all():
-            works = [self._reduce_fn(ex.tr.flat_grad) for ex in opt.executors]
-            for w in works:
-                if w is not None:
-                    w.wait()
+        self.grad_scale, self.accumulate = float(grad_scale), bool(accumulate)
+        self.bucket_bytes = bucket_bytes
+        self._static = (self.s_z, self.s_ctx, self.s_hint, self.s_t, self.s_noise)
 
         hook, opt.pre_step_hook = opt.pre_step_hook, None
         self._hook = hook
-        side = torch.cuda.Stream()
+        self._side = side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                fwd_bwd()
+                self._fwd_bwd(self._static)
                 if mode != "one":
-                    reduce_all()
+                    self._reduce_all()
                 opt.step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.segments = []               # [(graph, executor index or None, lo, hi)]
         self.g_b = None
-        if mode == "one":
+        self.g_z = None                  # accumulate=True: zero_grad as a piece of its own
+        self.captured = False
+        self.warmup_steps = warmup
+        if capture:
+            self.capture()
+
+    def _fwd_bwd(self, tensors, zero=True):
+        """[zero_grad,] forward, loss, backward on `tensors` = (z, ctx, hint, t, noise): the gradients are ADDED to the flat
+        buffer.  Returns (loss scalar, {loss_simple, loss_vlb, loss} or None without the direct path), device tensors."""
+        z, ctx, hint, t, noise = tensors
+        model, gs = self.model, self.grad_scale
+        if zero:
+            self.opt.zero_grad()
+        cond = {"c_crossattn": [ctx], "c_concat": [hint]}
+        direct = getattr(model, "engine_train_step", None)
+        if direct is not None:
+            # p_losses + backward without autograd: the captured region holds hand-written kernel nodes only
+            # (no ATen launch, no memset node); out = {loss_simple, loss_vlb, loss}
+            loss3 = direct(z, cond, t, noise) if gs == 1.0 else direct(z, cond, t, noise, grad_scale=gs)
+            return loss3[2], loss3
+        loss, _ = model.p_losses(z, cond, t, noise=noise)
+        (loss if gs == 1.0 else loss * gs).backward()
+        return loss.detach(), None
+
+    def _reduce_all(self):
+        works = [self._reduce_fn(ex.tr.flat_grad) for ex in self.opt.executors]
+        for w in works:
+            if w is not None:
+                w.wait()
+
+    def eager(self, z, cond_txt, hint, t, noise, first: bool = True, last: bool = True):
+        """One micro-step with ordinary launches on the caller's tensors (any shapes): what a replay computes, for the steps
+        that warm the allocations before capture() and for batches whose shapes are not the captured ones.  Runs on this
+        object's side stream, fenced against the current stream on both ends.  Returns {loss_simple, loss_vlb, loss} where the
+        model has the direct path, else the loss scalar."""
+        cur = torch.cuda.current_stream()
+        self._side.wait_stream(cur)
+        with torch.cuda.stream(self._side):
+            loss, loss3 = self._fwd_bwd((z, cond_txt, hint, t, noise), zero=first)
+            out = loss3 if loss3 is not None else loss
+            if last:
+                if self.mode != "one":
+                    self._reduce_all()
+                self.opt.step()
+        cur.wait_stream(self._side)
+        return out
+
+    def capture(self):
+        """Record the graphs on the static tensors.  Capturing executes nothing."""
+        assert not self.captured, "captured already"
+        opt, mode = self.opt, self.mode
+
+        def fwd_bwd():
+            loss, self.loss3 = self._fwd_bwd(self._static, zero=not self.accumulate)
+            return loss
+        torch.cuda.synchronize()
+        opt.sync_hyper()
+        if self.accumulate:
+            self.g_z = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_z, capture_error_mode=self.capture_error_mode):
+                opt.zero_grad()
+            if mode == "segmented":
+                self._capture_segments(fwd_bwd, max(1, self.bucket_bytes // 4))
+                pool = self._pool
+            else:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self.g_z.pool(), capture_error_mode=self.capture_error_mode):
+                    self.loss = fwd_bwd()
+                self.segments.append((g, "all" if mode == "two" else None, 0, 0))
+                pool = self.g_z.pool()
+            self.g_b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_b, pool=pool, capture_error_mode=self.capture_error_mode):
+                opt.step()
+        elif mode == "one":
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
                 self.loss = fwd_bwd()
@@ -415,11 +485,11 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.g_b, pool=g.pool(), capture_error_mode=self.capture_error_mode):
                 opt.step()
         else:
-            self._capture_segments(fwd_bwd, max(1, bucket_bytes // 4))
+            self._capture_segments(fwd_bwd, max(1, self.bucket_bytes // 4))
             self.g_b = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_b, pool=self._pool, capture_error_mode=self.capture_error_mode):
                 opt.step()
-        self.warmup_steps = warmup
+        self.captured = True
 
     def _capture_segments(self, fwd_bwd, bucket_elems):
         """Capture forward + backward as consecutive graphs that end where a gradient bucket is complete.  The
@@ -483,12 +553,38 @@ class GraphedTrainStep:
             for ex, h in zip(execs, saved_hooks):
                 ex.on_stage_done = h
 
+    def matches(self, z, cond_txt, hint, t, noise) -> bool:
+        """Do these tensors have the shapes and dtypes the graphs were captured on?"""
+        return all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip((z, cond_txt, hint, t, noise), self._static))
+
     def __call__(self, z, cond_txt, hint, t, noise):
+        if self.accumulate:
+            return self.micro(z, cond_txt, hint, t, noise)[2]
         self.s_z.copy_(z); self.s_ctx.copy_(cond_txt); self.s_hint.copy_(hint)
         self.s_t.copy_(t); self.s_noise.copy_(noise)
         self.opt.sync_hyper()
         replay_with_exchange(self.segments, self.g_b, self.opt.executors, self._reduce_fn)
         return self.loss
+
+    def micro(self, z, cond_txt, hint, t, noise, first: bool = True, last: bool = True):
+        """Replay one micro-step of an optimizer step and return the loss 3-vector (overwritten by the next replay).
+        `first`: clear the gradients before; `last`: exchange the gradient buckets between the segments and run the optimizer
+        piece after.  Without accumulate=True there is one form only, the whole optimizer step."""
+        if not self.accumulate:
+            assert first and last, "captured as one optimizer step per replay: build with accumulate=True"
+            self(z, cond_txt, hint, t, noise)
+            return self.loss3
+        self.s_z.copy_(z); self.s_ctx.copy_(cond_txt); self.s_hint.copy_(hint)
+        self.s_t.copy_(t); self.s_noise.copy_(noise)
+        if first:
+            self.g_z.replay()
+        if last:
+            self.opt.sync_hyper()
+            replay_with_exchange(self.segments, self.g_b, self.opt.executors, self._reduce_fn)
+        else:
+            for g, _, _, _ in self.segments:      # gradients stay local until the last micro-step
+                g.replay()
+        return self.loss3
 
 
 def replay_with_exchange(segments, g_opt, execs, reduce_fn):

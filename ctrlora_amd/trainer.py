@@ -12,6 +12,9 @@ Semantics kept from Lightning 1.5: the loss of each micro-batch is divided by `a
 `global_step` counts OPTIMIZER steps; callbacks get `on_train_batch_end(trainer, module, outputs, batch, batch_idx)`
 after every micro-batch and `on_batch_end(trainer, module)` (what `CheckpointEveryNSteps` hooks); checkpoints are
 `{"state_dict", "global_step", "epoch", "optimizer_states"}` and resumable with `fit(..., ckpt_path=)`.
+
+`graph_step=True` (LoRA fine-tuning on a GPU only; off by default) replays the optimizer step as hipGraphs
+(`ctrlora_amd.train.GraphedTrainStep`) instead of launching its ~1900 kernels one by one: see `Trainer._fit_graphed`.
 """
 from __future__ import annotations
 
@@ -28,10 +31,30 @@ class _CheckpointDir:
         self.dirpath, self.filename = dirpath, "last.ckpt"
 
 
+_GRAPH_OPTIONS = ("split_graphs", "bucket_bytes", "reduce_fn", "warm_steps")
+
+
+def graph_step_refusal(model) -> Optional[str]:
+    """Why `graph_step` cannot run this model, in one line, or None.  Checked before the first step: nothing falls back to
+    the eager loop in the middle of a run."""
+    cm = getattr(model, "control_model", None)
+    if callable(getattr(model, "init_data_parallel", None)) or hasattr(cm, "switch_lora"):
+        return ("multi-task pre-training switches the LoRA bank from step to step (ctrlora_amd.train.GraphedPretrainStep is "
+                "single-process): it keeps the eager loop")
+    if not callable(getattr(model, "engine_train_step", None)):
+        return f"{type(model).__name__} has no engine_train_step (the step without torch.autograd that a capture needs)"
+    if getattr(model, "loss_type", "l2") != "l2":
+        return f"engine_train_step computes the l2 loss only, the model's loss_type is '{model.loss_type}'"
+    if float(getattr(model, "original_elbo_weight", 0.0)) != 0.0:
+        return f"engine_train_step leaves the elbo term out, the model's original_elbo_weight is {model.original_elbo_weight}"
+    return None
+
+
 class Trainer:
     def __init__(self, max_steps: int = 100000, accumulate_grad_batches: int = 1, precision=32,
                  callbacks: Sequence = (), default_root_dir: str = "runs/default", device: Optional[str] = None,
-                 strategy: str = "ddp", accelerator: str = "gpu", devices=-1, log_every_n_steps: int = 50):
+                 strategy: str = "ddp", accelerator: str = "gpu", devices=-1, log_every_n_steps: int = 50,
+                 graph_step=False):
         self.max_steps = int(max_steps)
         self.accumulate_grad_batches = max(1, int(accumulate_grad_batches))
         self.precision = precision
@@ -49,6 +72,17 @@ class Trainer:
         self.model = None
         self.optimizer = None
         self.logged = []
+        # graph_step: False = the eager loop; True or a dict of options = captured steps (_fit_graphed)
+        self.graph_step = bool(graph_step) or isinstance(graph_step, dict)
+        self._graph_opts = dict(graph_step) if isinstance(graph_step, dict) else {}
+        unknown = set(self._graph_opts) - set(_GRAPH_OPTIONS)
+        if unknown:
+            raise ValueError(f"graph_step: unknown option(s) {sorted(unknown)}; known: {list(_GRAPH_OPTIONS)}")
+        if self.graph_step and self.device.type != "cuda":
+            raise ValueError(f"graph_step needs a GPU: a hipGraph cannot be captured on device '{self.device}'")
+        self.graph_replays = 0          # optimizer steps whose every micro-step was a replay
+        self.graph_eager_steps = 0      # optimizer steps with at least one eagerly launched micro-step (warm-up, other shapes)
+        self.graph_mode = "off"         # "one" | "segmented" once the step object exists
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -115,6 +149,10 @@ class Trainer:
     # ------------------------------------------------------------------ the loop
     def fit(self, model, train_dataloader, ckpt_path: Optional[str] = None):
         self.model = model
+        if self.graph_step:
+            why = graph_step_refusal(model)
+            if why is not None:
+                raise ValueError("graph_step refused: " + why)
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)
         model.to(self.device).train()
@@ -126,6 +164,8 @@ class Trainer:
         self.optimizer = opt[0] if isinstance(opt, (list, tuple)) else opt
         if ck is not None:
             self._restore_optimizer(ck)
+        if self.graph_step:
+            return self._fit_graphed(model, train_dataloader)
         acc = self.accumulate_grad_batches
         dp = getattr(model, "dp", None)
         self.optimizer.zero_grad()
@@ -152,6 +192,89 @@ class Trainer:
                         self.logged.append((self.global_step, float(loss.detach())))
                         print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss.detach()):.5f}")
                 self._call("on_train_batch_end", model, {"loss": loss.detach()}, batch, batch_idx)
+                self._call("on_batch_end", model)
+                if self.global_step >= self.max_steps:
+                    break
+            if seen == 0:
+                raise RuntimeError("empty dataloader")
+            self.current_epoch += 1
+            model.current_epoch = self.current_epoch
+        self._call("on_train_end", model)
+        return self
+
+    # ------------------------------------------------------------------ the loop, optimizer step as hipGraph replays
+    def _make_graph_step(self, model, tensors):
+        """The step object of `_fit_graphed`: nothing run, nothing captured yet."""
+        from ctrlora_amd.train import GraphedTrainStep
+        o = self._graph_opts
+        acc = self.accumulate_grad_batches
+        return GraphedTrainStep(model, self.optimizer, *tensors, warmup=0, capture=False, accumulate=acc > 1, grad_scale=1.0 / acc,
+                                split_graphs=o.get("split_graphs"), bucket_bytes=o.get("bucket_bytes", 32 << 20),
+                                reduce_fn=o.get("reduce_fn"))
+
+    @torch.no_grad()
+    def _graph_inputs(self, model, batch):
+        """Everything of a micro-step that is NOT replayed, in the eager path's order: get_input (first stage or cached
+        posteriors: CPU-generator draws, target first; text encoder), the hint latent (second CPU-generator draw), then t and the
+        q_sample noise on the device generator with LatentDiffusion.forward's and p_losses' own calls -- one seed, one stream of
+        numbers in both modes."""
+        z, cond = model.get_input(batch, model.first_stage_key)
+        hint = model._hint_latent(cond)
+        cc = cond["c_crossattn"]
+        ctx = cc[0] if len(cc) == 1 else torch.cat(cc, 1)
+        t = torch.randint(0, model.num_timesteps, (z.shape[0],), device=model.device).long()
+        noise = torch.randn_like(z)
+        return z, ctx, hint, t, noise
+
+    def _fit_graphed(self, model, train_dataloader):
+        """`fit` with graph_step on.  Per micro-batch: `_graph_inputs` outside any capture, then the forward + loss + backward
+        (and, on the last micro-batch of an optimizer step, the gradient exchange and AdamW + re-pack) through the step object.
+
+        No batch is spent on warm-up: the first `warm_steps` (default 2) optimizer steps of this fit launch eagerly on the same
+        direct path, each micro-step on its own batch; the graphs are captured (capturing executes nothing) before the next one
+        and replayed from there on.  A batch whose tensor shapes are not the captured ones is launched eagerly too, and counted:
+        `graph_eager_steps` / `graph_replays` count optimizer steps.  Accumulation (Lightning 1.5): the first micro-step clears
+        the gradients, every micro-step's gradient is scaled by 1 / acc, the exchange and the optimizer follow the last one.
+        The host is not synchronized here beyond what the eager loop does (log_dict, the logged loss)."""
+        acc = self.accumulate_grad_batches
+        warm = max(0, int(self._graph_opts.get("warm_steps", 2)))
+        step = None
+        micro = steps_here = 0
+        launched_eagerly = False
+        while self.global_step < self.max_steps:
+            sampler = getattr(train_dataloader, "sampler", None)
+            if hasattr(sampler, "set_epoch"):
+                sampler.set_epoch(self.current_epoch)
+            seen = 0
+            for batch_idx, batch in enumerate(train_dataloader):
+                seen += 1
+                first, last = micro % acc == 0, (micro + 1) % acc == 0
+                tensors = self._graph_inputs(model, batch)
+                if step is None:
+                    step = self._graph_step_obj = self._make_graph_step(model, tensors)
+                    self.graph_mode = "one" if step.mode == "one" else "segmented"
+                if first and not step.captured and steps_here >= warm and step.matches(*tensors):
+                    step.capture()
+                replay = step.captured and step.matches(*tensors)
+                loss3 = (step.micro if replay else step.eager)(*tensors, first=first, last=last)
+                launched_eagerly |= not replay
+                micro += 1
+                loss3 = loss3.clone()                   # a replay overwrites its output: callbacks may keep theirs
+                loss = loss3[2]
+                model.log_dict({"train/loss_simple": loss3[0], "train/loss_vlb": loss3[1], "train/loss": loss})
+                if last:
+                    self.global_step += 1
+                    steps_here += 1
+                    model.global_step = self.global_step
+                    if launched_eagerly:
+                        self.graph_eager_steps += 1
+                    else:
+                        self.graph_replays += 1
+                    launched_eagerly = False
+                    if self.is_global_zero and self.global_step % self.log_every_n_steps == 0:
+                        self.logged.append((self.global_step, float(loss)))
+                        print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss):.5f}")
+                self._call("on_train_batch_end", model, {"loss": loss}, batch, batch_idx)
                 self._call("on_batch_end", model)
                 if self.global_step >= self.max_steps:
                     break

@@ -48,6 +48,11 @@ def get_parser():
     p.add_argument("--latent_cache", type=str, default=None,
                    help="directory written by scripts/tool_cache_latents.py for this dataroot: train from the stored first-stage "
                         "posteriors, so that no step runs the VAE encoder (CustomDataset only; off by default)")
+    p.add_argument("--graph", action="store_true", default=False,
+                   help="capture the optimizer step (forward, loss, backward, gradient exchange points, AdamW, re-pack) as "
+                        "hipGraphs after two eagerly launched steps and replay it for every later batch instead of launching its "
+                        "~1900 kernels from Python; the data loading, the first stage and the text encoder stay outside the "
+                        "capture (GPU only; works with --latent_cache, --gradacc and torchrun; off by default)")
     return p
 
 
@@ -134,8 +139,12 @@ def main(argv=None):
     trainer = Trainer(max_steps=args.max_steps, accumulate_grad_batches=args.gradacc, precision=args.precision,
                       callbacks=[ImageLogger(batch_frequency=args.img_logger_freq),
                                  CheckpointEveryNSteps(save_step_frequency=args.ckpt_logger_freq)],
-                      default_root_dir=os.path.join("runs", name))
+                      default_root_dir=os.path.join("runs", name), graph_step=bool(args.graph))
     trainer.fit(model, loader)
+    if args.graph and rank == 0:
+        print(f"[trainer] graph mode '{trainer.graph_mode}': {trainer.graph_replays} optimizer steps replayed, "
+              f"{trainer.graph_eager_steps} launched eagerly")
+    return trainer
 
 
 if __name__ == "__main__":
