@@ -63,7 +63,8 @@ class ControlNet(nn.Module, EngineHost):
 
     def _on_state_loaded(self):
         """Keep the executor (an optimizer may hold its flat master / gradient buffers): the bound trainable
-        Parameters wrote through to the masters during the load; frozen weights are re-packed in place."""
+        Parameters wrote through to the masters during the load; frozen weights and the packs derived from them are re-packed in
+        place (the address rule of ctrlora_amd/engine/packing.py), so a captured training step stays valid."""
         ex = self.__dict__.get("_exec")
         if ex is not None:
             ex.reload_frozen(self._executor_state())

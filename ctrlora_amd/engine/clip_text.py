@@ -210,7 +210,7 @@ class ClipTextE:
         return out
 
     def load(self, state_dict: Dict[str, torch.Tensor]):
-        """Refresh the packed weights in place (the addresses a captured graph replays stay valid)."""
+        """Refresh the packed weights in place (the address rule of engine/packing.py: a captured graph keeps replaying them)."""
         new = pack_clip_text(state_dict, self.cfg)
         if set(new) != set(self.w):
             raise ValueError("the state dict gains or loses text_projection.weight: build a new executor")

@@ -290,8 +290,8 @@ class _Conv:
         self.cw, self.mode = cw, mode
         self.cout = cw.O
         # the source-grid forms of Upsample / Downsample (blocks._phase_ok) use weights derived from the packed ones: built here,
-        # not on first use, so that a first call inside a hipGraph capture does not record the packing kernels into the graph
-        # (a conv that is made trainable afterwards never uses them)
+        # not on first use, so that a first call inside a hipGraph capture does not record the packing kernels into the graph.
+        # Conv3W.load() refreshes them in place from then on (a conv that is made trainable afterwards never uses them)
         from .blocks import CONV_PHASE
         if CONV_PHASE and cw.tW is None:
             if mode == hip.CONV_UP2:
@@ -510,7 +510,8 @@ class ControlNetE:
 
     def reload_frozen(self, sd):
         """module.load_state_dict() happened after this executor was built: refresh the packed frozen weights in
-        place (the trainables are views of the flat masters the Parameters write through) and re-pack."""
+        place (the trainables are views of the flat masters the Parameters write through) and re-pack.  No packed tensor
+        moves -- the address rule of packing.py -- so a step captured before the load replays the new weights."""
         self._b.reload_frozen({k: v for k, v in sd.items()})
         self.repack()
 
@@ -581,7 +582,7 @@ class ControlNetE:
         for L in self._b.linears:
             if self.merge_lora:
                 L.merge_lora()
-            L.invalidate_geglu()     # permuted (GEGLU-fused) copies are rebuilt lazily from the fresh B
+            L.invalidate_geglu()     # permuted (GEGLU-fused) copies are stale: refreshed in place at their next use
 
     def fwd(self, ctx: Ctx, hint_tok, t, c, B, H, W, sinks, scales, weight=1.0, kv=None):
         """sinks[k] = (out_view, residual_view or None); out = (zero_conv_k(h_k)) * scale_k * weight + residual."""

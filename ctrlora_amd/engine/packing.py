@@ -13,6 +13,12 @@ cldm/cldm_ctrlora_finetune.py:84-108) live in ONE flat fp32 master buffer with O
 gradient buffer (ordered by backward completion so that the DP all-reduce can be bucketed and
 overlapped); their packed copies are refreshed after every optimizer step by the pack /
 transpose kernels.
+
+THE ADDRESS RULE.  A tensor of a packed object whose address has been handed to a launch is rewritten IN PLACE and never
+replaced: a captured graph (the graphed training step, the samplers) and the re-pack descriptor tables keep the pointer, not
+the Python object.  It holds for the packed copies (`load`, `repack`: copy_ / pack kernels into the existing buffers) and for
+the packs DERIVED from them -- Conv3W's phase packs, LinearW's GEGLU pack, the folded Wm: a refresh recomputes the values and
+writes them into the storage that already exists.
 """
 from __future__ import annotations
 
@@ -114,10 +120,12 @@ class LinearW:
         self.tW: Optional[Trainable] = None
         self.tb: Optional[Trainable] = None
         self.dtype = dtype
+        self._geglu = None                      # (Wg, bg, Bg) of geglu_pack(): built on first use, refreshed in place when stale
+        self._geglu_stale = False
 
     def load(self, W: torch.Tensor, bias: Optional[torch.Tensor]):
         """Refresh the packed copies of a FROZEN weight in place (module.load_state_dict after the executor was
-        built: the optimizer keeps pointing at the same executor / flat buffers)."""
+        built; the address rule of the module docstring)."""
         W = W.reshape(W.shape[0], -1).to(device=self.W.device, dtype=torch.float32)
         assert tuple(W.shape) == (self.N, self.K)
         self.W.copy_(W)
@@ -135,21 +143,33 @@ class LinearW:
         return self.N % 320 == 0 and (self.N // 2) % 80 == 0
 
     def geglu_pack(self):
-        g = self.__dict__.get("_geglu")
-        if g is None:
+        """(Wg, bg, Bg).  Built on first use and kept lazy (training re-packs every step and never uses it); once
+        invalidate_geglu() has marked it stale, the next call rewrites the SAME tensors (the address rule).  Which weight
+        feeds it (W, or the folded Wm) and whether bg / Bg exist are settled by the first build: executors fold or attach the
+        LoRA at construction, before any forward."""
+        srcs = (self.W if self.Wm is None else self.Wm, self.bias, self.B if (self.r and self.Wm is None) else None)
+        if self._geglu is None:
             half = self.N // 2
             j = torch.arange(half // 80, device=self.W.device).repeat_interleave(160)
             c = torch.arange(160, device=self.W.device).repeat(half // 80)
-            perm = torch.where(c < 80, j * 80 + c, half + j * 80 + (c - 80))
-            Wg = (self.W if self.Wm is None else self.Wm).index_select(0, perm).contiguous()
-            bg = None if self.bias is None else self.bias.index_select(0, perm).contiguous()
-            Bg = self.B.index_select(0, perm).contiguous() if (self.r and self.Wm is None) else None
-            g = (Wg, bg, Bg)
-            self.__dict__["_geglu"] = g
-        return g
+            self._geglu_perm = torch.where(c < 80, j * 80 + c, half + j * 80 + (c - 80))
+            self._geglu_folded = self.Wm is not None
+            self._geglu = tuple(None if s is None else s.index_select(0, self._geglu_perm) for s in srcs)
+        elif self._geglu_stale:
+            if self._geglu_folded != (self.Wm is not None) or any((s is None) != (g is None) for s, g in zip(srcs, self._geglu)):
+                raise RuntimeError("the GEGLU pack cannot be refreshed in place: it was built from %s with (Wg, bg, Bg) = %s, the "
+                                   "linear now offers %s with %s (fold or attach the LoRA before the first forward)"
+                                   % ("Wm" if self._geglu_folded else "W", [g is not None for g in self._geglu],
+                                      "W" if self.Wm is None else "Wm", [s is not None for s in srcs]))
+            for s, g in zip(srcs, self._geglu):
+                if g is not None:
+                    torch.index_select(s, 0, self._geglu_perm, out=g)
+        self._geglu_stale = False
+        return self._geglu
 
     def invalidate_geglu(self):
-        self.__dict__.pop("_geglu", None)
+        """The pack's sources changed: mark it stale.  Its storage stays."""
+        self._geglu_stale = True
 
     def attach_lora(self, tA: Trainable, tB: Trainable, device):
         self.tA, self.tB = tA, tB
@@ -168,7 +188,7 @@ class LinearW:
         if self.Wm is None:
             self.Wm = m.to(self.dtype).contiguous()
         else:
-            self.Wm.copy_(m)
+            self.Wm.copy_(m)             # the address rule: same tensor at every later fold
         self.invalidate_geglu()
 
     def attach_trainable_weight(self, tW: Trainable, tb: Optional[Trainable]):
@@ -241,6 +261,59 @@ class LoraGroup:
                 L.Wm = self.Wm[g * self.N:(g + 1) * self.N]
 
 
+# ---- Conv3W's phase packs: pure functions of the packed forward weights Wp [Op][ky][kx][Ip] -> a new tensor in Wp's dtype.
+# Coincident taps are SUMMED in fp32 and rounded once to the storage dtype.
+
+def _taps(Wp: torch.Tensor) -> torch.Tensor:
+    return Wp.float().view(Wp.shape[0], 3, 3, Wp.shape[1] // 9)               # [o][ky][kx][i]
+
+
+def _phase_up2(Wp: torch.Tensor) -> torch.Tensor:
+    """Upsample.conv over the nearest-x2 input (openaimodel.py:108-118): output pixel (2y + a, 2x + b) reads source rows
+    {y - 1, y} (a = 0: tap ky = 0 | taps 1 + 2) or {y, y + 1} (a = 1: taps 0 + 1 | tap 2), columns likewise: the 3x3 taps that
+    land on one source pixel are summed.  [4 phases][Op][2x2][Ip], flat."""
+    W = _taps(Wp)
+    Op, Ip = W.shape[0], W.shape[3]
+    grp = {(0, 0): [0], (0, 1): [1, 2], (1, 0): [0, 1], (1, 1): [2]}
+    out = torch.empty(4, Op, 4, Ip, dtype=torch.float32, device=W.device)
+    for a in range(2):
+        for b in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    out[2 * a + b, :, 2 * ty + tx] = W[:, grp[(a, ty)]][:, :, grp[(b, tx)]].sum(dim=(1, 2))
+    return out.reshape(-1).to(Wp.dtype).contiguous().view(1, -1)              # (ldw1 is not used by this mode)
+
+
+def _phase_t2(Wp: torch.Tensor) -> torch.Tensor:
+    """Data gradient of Downsample's stride-2 conv (openaimodel.py:150; in = 2 out + k - 1): an even input row gets tap ky = 1
+    of output row y, an odd one tap 2 of row y and tap 0 of row y + 1.  Phase (a, b): [Ip][(1 + a)(1 + b)][Op], concatenated."""
+    W = _taps(Wp)
+    taps = {0: [1], 1: [2, 0]}                                                # window offset 0, +1 -> forward tap index
+    blocks = []
+    for a in range(2):
+        for b in range(2):
+            blk = torch.stack([W[:, ky, kx].t() for ky in taps[a] for kx in taps[b]], dim=1)   # [Ip][nt][Op]
+            blocks.append(blk.reshape(-1))
+    return torch.cat(blocks).to(Wp.dtype).contiguous().view(1, -1)            # (ldw1 is not used by this mode)
+
+
+def _phase_up2d(Wp: torch.Tensor) -> torch.Tensor:
+    """Data gradient of 'up2' on the source grid (CL_GEMM_CONV_S2K4): window row ky4 = 0..3 <-> upsampled row 2y - 1 + ky4,
+    which the forward reached from (phase a, window tap ty) = (1, 1), (0, 1), (1, 0), (0, 0): taps {2}, {1, 2}, {0, 1}, {0}.
+    [Ip][4x4][Op]."""
+    W = _taps(Wp)
+    Op, Ip = W.shape[0], W.shape[3]
+    grp4 = [[2], [1, 2], [0, 1], [0]]
+    out = torch.empty(Ip, 4, 4, Op, dtype=torch.float32, device=W.device)
+    for ky4 in range(4):
+        for kx4 in range(4):
+            out[:, ky4, kx4] = W[:, grp4[ky4]][:, :, grp4[kx4]].sum(dim=(1, 2)).t()
+    return out.reshape(Ip, 16 * Op).to(Wp.dtype).contiguous()
+
+
+_PHASE_BUILDERS = {"up2": _phase_up2, "t2": _phase_t2, "up2d": _phase_up2d}
+
+
 class Conv3W:
     """3x3 conv in implicit-GEMM form; channels padded to multiples of 32 where needed."""
 
@@ -253,52 +326,15 @@ class Conv3W:
         self.bias = torch.zeros(self.Op, dtype=torch.float32, device=device)
         self.tW: Optional[Trainable] = None     # trainable weight (Base-ControlNet pre-training), master [O][9][Ip]
         self.tb: Optional[Trainable] = None
-        self._phase = {}                        # phase-packed forms (phase_weights), built on first use, dropped by load()
+        self._phase = {}                        # phase-packed forms (phase_weights), built on first use, refreshed in place by load()
         self.load(W, bias)
 
     def phase_weights(self, kind: str) -> torch.Tensor:
-        """Weights of the phase-decomposed products (include/ctrlora_hip.h: CL_GEMM_CONV_UP2P / T2P), built once from the packed
-        forward weights of a FROZEN conv.
-
-        'up2' (Upsample.conv over the nearest-x2 input, openaimodel.py:108-118): output pixel (2y + a, 2x + b) reads source
-        rows {y - 1, y} (a = 0: tap ky = 0 | taps 1 + 2) or {y, y + 1} (a = 1: taps 0 + 1 | tap 2), columns likewise: the 3x3
-        taps that land on one source pixel are SUMMED (fp32, one rounding to the compute dtype).  [4 phases][Op][2x2][Ip].
-        't2' (data gradient of Downsample's stride-2 conv, :150; in = 2 out + k - 1): an even input row gets tap ky = 1 of
-        output row y, an odd one tap 2 of row y and tap 0 of row y + 1.  Phase (a, b): [Ip][(1 + a)(1 + b)][Op], concatenated."""
-        if kind in self._phase:
-            return self._phase[kind]
-        assert self.tW is None, "phase-packed weights are built once: frozen convs only"
-        W = self.Wp.float().view(self.Op, 3, 3, self.Ip)                     # [o][ky][kx][i]
-        if kind == "up2":
-            grp = {(0, 0): [0], (0, 1): [1, 2], (1, 0): [0, 1], (1, 1): [2]}
-            out = torch.empty(4, self.Op, 4, self.Ip, dtype=torch.float32, device=W.device)
-            for a in range(2):
-                for b in range(2):
-                    for ty in range(2):
-                        for tx in range(2):
-                            out[2 * a + b, :, 2 * ty + tx] = W[:, grp[(a, ty)]][:, :, grp[(b, tx)]].sum(dim=(1, 2))
-            packed = out.reshape(-1)
-        elif kind == "t2":
-            taps = {0: [1], 1: [2, 0]}                                        # window offset 0, +1 -> forward tap index
-            blocks = []
-            for a in range(2):
-                for b in range(2):
-                    blk = torch.stack([W[:, ky, kx].t() for ky in taps[a] for kx in taps[b]], dim=1)   # [Ip][nt][Op]
-                    blocks.append(blk.reshape(-1))
-            packed = torch.cat(blocks)
-        elif kind == "up2d":
-            # data gradient of 'up2' on the source grid (CL_GEMM_CONV_S2K4): window row ky4 = 0..3 <-> upsampled row 2y - 1 + ky4,
-            # which the forward reached from (phase a, window tap ty) = (1, 1), (0, 1), (1, 0), (0, 0): taps {2}, {1, 2}, {0, 1}, {0}
-            grp4 = [[2], [1, 2], [0, 1], [0]]
-            out = torch.empty(self.Ip, 4, 4, self.Op, dtype=torch.float32, device=W.device)
-            for ky4 in range(4):
-                for kx4 in range(4):
-                    out[:, ky4, kx4] = W[:, grp4[ky4]][:, :, grp4[kx4]].sum(dim=(1, 2)).t()
-            self._phase[kind] = out.reshape(self.Ip, 16 * self.Op).to(self.Wp.dtype).contiguous()
-            return self._phase[kind]
-        else:
-            raise ValueError(kind)
-        self._phase[kind] = packed.to(self.Wp.dtype).contiguous().view(1, -1)     # (ldw1 is not used by these modes)
+        """Weights of the phase-decomposed products (include/ctrlora_hip.h: CL_GEMM_CONV_UP2P / T2P / S2K4) of a FROZEN conv,
+        derived from the packed forward weights by _PHASE_BUILDERS[kind]: built on first use, refreshed in place by load()."""
+        if kind not in self._phase:
+            assert self.tW is None, "phase-packed weights follow load() only: frozen convs only"
+            self._phase[kind] = _PHASE_BUILDERS[kind](self.Wp)
         return self._phase[kind]
 
     def attach_trainable(self, tW: Trainable, tb: Trainable):
@@ -316,9 +352,9 @@ class Conv3W:
         return rows
 
     def load(self, W: torch.Tensor, bias: torch.Tensor):
-        """(Re)pack in place: [O][ky][kx][I] and the tap-flipped data-gradient form [I][2-ky][2-kx][O]."""
+        """(Re)pack in place: [O][ky][kx][I], the tap-flipped data-gradient form [I][2-ky][2-kx][O], and every phase pack that
+        has been built (the address rule; eagerly, so that a later first use inside a capture records nothing)."""
         device = self.Wp.device
-        self._phase = {}
         W = W.to(device=device, dtype=torch.float32)
         assert W.shape[0] == self.O and W.shape[1] == self.I
         Wpad = torch.zeros(self.Op, self.Ip, 3, 3, dtype=torch.float32, device=device)
@@ -327,6 +363,10 @@ class Conv3W:
         if self.Wd is not None:
             self.Wd.copy_(Wpad.flip(2, 3).permute(1, 2, 3, 0).reshape(self.Ip, 9 * self.Op))
         self.bias[:self.O] = bias.to(device=device, dtype=torch.float32)
+        if self.tW is not None:
+            self._phase.clear()                 # made trainable since: re-packed every step, never uses them again
+        for kind, pack in self._phase.items():
+            pack.copy_(_PHASE_BUILDERS[kind](self.Wp))
 
 
 class NormW:

@@ -149,7 +149,7 @@ class ClipVisionE:
         return out
 
     def load(self, state_dict: Dict[str, torch.Tensor]):
-        """Refresh the packed weights in place (the addresses a captured graph replays stay valid)."""
+        """Refresh the packed weights in place (the address rule of engine/packing.py: a captured graph keeps replaying them)."""
         new = pack_clip_vision(state_dict, self.cfg)
         for k, t in new.items():
             if k != "layers":
