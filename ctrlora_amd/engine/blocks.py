@@ -147,29 +147,38 @@ class Ctx:
 
 # --------------------------------------------------------------------------- linear
 
+def folded(ctx: Ctx, L) -> bool:
+    """Does this pass read L's LoRA (L: a LinearW or a packing.LoraGroup) folded into the weight -- an inference executor
+    packed Wm = W + B A and no backward is being recorded -- instead of as a live second K segment?  THE one spelling of it."""
+    return L.Wm is not None and not ctx.record
+
+
 def linear_fwd(ctx: Ctx, L: LinearW, x, out=None, residual=None, act=hip.ACT_NONE, alpha=1.0, beta=1.0,
-               out_f32=False, alpha_n=0, ln=None):
-    """y = (x W^T + b [+ (x A^T) B^T]) * alpha + beta * residual.  Returns (y, t = x A^T or None).
+               out_f32=False, alpha_n=0, ln=None, pack=None):
+    """y = act(x W^T + b [+ (x A^T) B^T]) * alpha + beta * residual.  Returns (y, t = x A^T or None).  The ONE place that
+    launches a single linear's product: folded (Wm), or live LoRA (t = x A^T, then [x | t] . [W | B]^T).
     alpha_n > 0: alpha multiplies output columns [0, alpha_n) only (the q part of a fused q | k | v).
-    ln = (gamma, beta, eps, stats): x is UN-normalised and LayerNorm runs as the product's prologue (ln_prologue_ok)."""
+    ln = (gamma, beta, eps, stats): x is UN-normalised and LayerNorm runs as the product's prologue (ln_prologue_ok).
+    act = ACT_GEGLU / ACT_GEGLU_SPLIT: the product is L.N wide, y = value * gelu(gate) half of that.
+    pack = (weight, bias, up-factor or None) in place of L's own: the GEGLU-permuted L.geglu_pack()."""
     M = x.shape[0]
+    W, bias, Bu = pack if pack is not None else (L.Wm, L.bias, None) if folded(ctx, L) else (L.W, L.bias, L.B)
+    assert ln is None or Bu is None, "LayerNorm prologue: the product may not carry a live LoRA segment"
     t = None
-    merged = L.Wm is not None and not ctx.record      # inference executor: W + B A already folded
-    assert ln is None or not (L.r and not merged), "LayerNorm prologue: the product may not carry a live LoRA segment"
-    if L.r and not merged:
+    if Bu is not None:
         t = ctx.new(M, L.r)
         hip.gemm(x, L.A, t)
     if out is None:
-        out = ctx.new(M, L.N, torch.float32 if out_f32 else None)
-    hip.gemm(x, L.Wm if merged else L.W, out, a2=t, w2=L.B if t is not None else None, bias=L.bias, residual=residual,
-             alpha=alpha, beta=beta if residual is not None else 0.0, act=act, out_f32=out_f32, alpha_n=alpha_n, ln=ln)
+        out = ctx.new(M, L.N // 2 if act in (hip.ACT_GEGLU, hip.ACT_GEGLU_SPLIT) else L.N, torch.float32 if out_f32 else None)
+    hip.gemm(x, W, out, a2=t, w2=Bu, bias=bias, residual=residual, alpha=alpha, beta=beta if residual is not None else 0.0,
+             act=act, out_f32=out_f32, alpha_n=alpha_n, ln=ln, N=L.N)
     return out, t
 
 
 def input_live(ctx: Ctx, L: LinearW) -> bool:
     """Is the tensor L's product reads an operand of something else too -- t = x A^T of an unmerged LoRA, or the weight gradient
     of a dense weight that trains (pre-training / ft_with_lora = False)?  Then a LayerNorm in front of it must be materialised."""
-    return (bool(L.r) and not (L.Wm is not None and not ctx.record)) or (ctx.record and L.tW is not None)
+    return (bool(L.r) and not folded(ctx, L)) or (ctx.record and L.tW is not None)
 
 
 def ln_prologue_ok(ctx: Ctx, M: int, N: int, K: int, lora_live: bool, act=hip.ACT_NONE) -> bool:
@@ -184,7 +193,7 @@ def group_fwd(ctx: Ctx, grp, x, alpha=1.0, alpha_n=0, ln=None):
     alpha / alpha_n: as linear_fwd (the first member's output scaled in the product's epilogue)."""
     M = x.shape[0]
     y = ctx.new(M, grp.G * grp.N)
-    if grp.Wm is not None and not ctx.record:              # inference executor: W + B A folded, one plain product
+    if folded(ctx, grp):                                   # one plain product
         hip.gemm(x, grp.Wm, y, bias=grp.bias, alpha=alpha, alpha_n=alpha_n, ln=ln)
         return y, None
     assert ln is None, "LayerNorm prologue: the grouped product carries live LoRA segments"
@@ -194,16 +203,37 @@ def group_fwd(ctx: Ctx, grp, x, alpha=1.0, alpha_n=0, ln=None):
     return y, t
 
 
+def group_bwd(ctx: Ctx, grp, dy, need_dx=True, out=None, accum=None):
+    """Data gradient of a packing.LoraGroup: dy [M, G N] -> (dx [M, K] = [dy | u] . [W^T | A^T] (+ accum) or None, u [M, G r])."""
+    M = dy.shape[0]
+    u = ctx.new(M, grp.G * grp.r)
+    if grp.r % 64 == 0:
+        hip.gemm(dy, grp.Bt, u, k1=grp.N, a1_group_n=grp.r)
+    else:                                 # rank below the narrowest tile: one small product per member
+        for L, d, u_ in zip(grp.members, grp.split(dy), grp.split(u)):
+            hip.gemm(d, L.Bt, u_)
+    dx = None
+    if need_dx:
+        dx = ctx.new(M, grp.K) if out is None else out
+        hip.gemm(dy, grp.Wt, dx, a2=u, w2=grp.At, residual=accum, beta=1.0 if accum is not None else 0.0)
+    return dx, u
+
+
+def lora_up_bwd(ctx: Ctx, L: LinearW, dy):
+    """u = dy B [M, r]: what dA needs, and the second K segment of the data gradient.  None without a LoRA."""
+    if not L.r:
+        return None
+    u = ctx.new(dy.shape[0], L.r)
+    hip.gemm(dy, L.Bt, u)
+    return u
+
+
 def linear_bwd_data(ctx: Ctx, L: LinearW, dy, out=None, accum=None):
     """dx = dy W + (dy B) A (+ accum).  Returns (dx, u = dy B or None)."""
-    M = dy.shape[0]
-    u = None
-    if L.r:
-        u = ctx.new(M, L.r)
-        hip.gemm(dy, L.Bt, u)
+    u = lora_up_bwd(ctx, L, dy)
     if out is None:
-        out = ctx.new(M, L.K)
-    hip.gemm(dy, L.Wt, out, a2=u, w2=L.At if L.r else None, residual=accum, beta=1.0 if accum is not None else 0.0)
+        out = ctx.new(dy.shape[0], L.K)
+    hip.gemm(dy, L.Wt, out, a2=u, w2=L.At, residual=accum, beta=1.0 if accum is not None else 0.0)
     return out, u
 
 
@@ -221,6 +251,16 @@ def base_bwd_weight(ctx: Ctx, L: LinearW, x, dy):
     if L.tW is None:
         return
     dense_bwd_weight(ctx, L, x, dy, 1, dy.shape[0], 1.0)
+
+
+def linear_bwd(ctx: Ctx, L: LinearW, x, t, dy, out=None, accum=None):
+    """The whole backward of one linear, in this order: dx (linear_bwd_data), dB / dA (linear_bwd_lora), dW / db
+    (base_bwd_weight).  x, t: what linear_fwd read and returned.  Returns dx.  (A site that orders the three differently, or
+    shares a step with its siblings, spells its own sequence.)"""
+    dx, u = linear_bwd_data(ctx, L, dy, out=out, accum=accum)
+    linear_bwd_lora(ctx, L, x, t, dy, u)
+    base_bwd_weight(ctx, L, x, dy)
+    return dx
 
 
 def conv3_bwd_weight(ctx: Ctx, cw: Conv3W, x, dy, B, Hin, Win, mode=hip.CONV_S1):
@@ -438,9 +478,7 @@ class ResBlockE:
             hip.colsum(dh2, de32, B, HW)
             de = ctx.new(B, self.cout)
             hip.pack2d(de32, de)
-            _, u = linear_bwd_data(ctx, self.emb, de, out=dsemb, accum=dsemb)
-            linear_bwd_lora(ctx, self.emb, semb, t_e, de, u)
-            base_bwd_weight(ctx, self.emb, semb, de)
+            linear_bwd(ctx, self.emb, semb, t_e, de, out=dsemb, accum=dsemb)
         if conv_in is not None:
             conv3_bwd_weight(ctx, self.conv1, conv_in[0], dh2, B, H, W)
         dh1 = conv3_bwd_data(ctx, self.conv1, dh2, B, H, W)
@@ -493,9 +531,6 @@ class AttnE:
     def _prescaled(self, ctx: Ctx) -> bool:
         return PRESCALE_Q and ctx.dtype == torch.bfloat16
 
-    def _group_fwd(self, ctx: Ctx, x, alpha=1.0, alpha_n=0, ln=None):
-        return group_fwd(ctx, self.group, x, alpha=alpha, alpha_n=alpha_n, ln=ln)
-
     def ln_fusable(self, ctx: Ctx, M: int) -> bool:
         """Can the LayerNorm in front of this attention be the prologue of the product that reads it (q | k | v of a
         self-attention, to_q of a cross-attention)?"""
@@ -503,26 +538,10 @@ class AttnE:
             if self.fused_qkv is not None:
                 return ln_prologue_ok(ctx, M, 3 * self.inner, self.fused_qkv.K, input_live(ctx, self.fused_qkv))
             if self.group is not None:
-                return ln_prologue_ok(ctx, M, 3 * self.inner, self.group.K, not (self.group.Wm is not None and not ctx.record)
+                return ln_prologue_ok(ctx, M, 3 * self.inner, self.group.K, not folded(ctx, self.group)
                                       or any(ctx.record and L.tW is not None for L in self.group.members))
             return False          # three separate products would each normalise the rows again
         return ln_prologue_ok(ctx, M, self.inner, self.q.K, input_live(ctx, self.q))
-
-    def _group_bwd(self, ctx: Ctx, dy, need_dx: bool, accum=None):
-        """dy [M, G N] -> (dx [M, K] (+ accum) or None, u [M, G r])."""
-        grp = self.group
-        M = dy.shape[0]
-        u = ctx.new(M, grp.G * grp.r)
-        if grp.r % 64 == 0:
-            hip.gemm(dy, grp.Bt, u, k1=grp.N, a1_group_n=grp.r)
-        else:                                 # rank below the narrowest tile: one small product per member
-            for g, L in enumerate(grp.members):
-                hip.gemm(dy[:, g * grp.N:(g + 1) * grp.N], L.Bt, u[:, g * grp.r:(g + 1) * grp.r])
-        dx = None
-        if need_dx:
-            dx = ctx.new(M, grp.K)
-            hip.gemm(dy, grp.Wt, dx, a2=u, w2=grp.At, residual=accum, beta=1.0 if accum is not None else 0.0)
-        return dx, u
 
     def project_context(self, ctx: Ctx, c):
         """K / V projections of the text context (identical for every denoising step)."""
@@ -530,9 +549,8 @@ class AttnE:
             kv, _ = linear_fwd(ctx, self.fused_kv, c)
             return kv[:, :self.inner], kv[:, self.inner:], None, None
         if self.group is not None and not self.is_self:
-            kv, t = self._group_fwd(ctx, c)
-            r = self.group.r
-            return (kv[:, :self.inner], kv[:, self.inner:], None if t is None else t[:, :r], None if t is None else t[:, r:])
+            kv, t = group_fwd(ctx, self.group, c)
+            return tuple(self.group.split(kv) + self.group.split(t))
         k, tk = linear_fwd(ctx, self.k, c)
         v, tv = linear_fwd(ctx, self.v, c)
         return k, v, tk, tv
@@ -555,11 +573,8 @@ class AttnE:
                 qkv, _ = linear_fwd(ctx, self.fused_qkv, xn, alpha=qa, alpha_n=inner if pre else 0, ln=ln)
                 q, k, v = qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:]
             elif self.group is not None:
-                qkv, t = self._group_fwd(ctx, xn, alpha=qa, alpha_n=inner if pre else 0, ln=ln)
-                q, k, v = qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:]
-                if t is not None:
-                    r = self.group.r
-                    tq, tk, tv = t[:, :r], t[:, r:2 * r], t[:, 2 * r:]
+                qkv, t = group_fwd(ctx, self.group, xn, alpha=qa, alpha_n=inner if pre else 0, ln=ln)
+                (q, k, v), (tq, tk, tv) = self.group.split(qkv), self.group.split(t)
             else:
                 assert ln is None
                 q, tq = linear_fwd(ctx, self.q, xn, alpha=qa)
@@ -583,9 +598,7 @@ class AttnE:
         Returns d(xn) (+ accum_xn)."""
         xn, c, q, k, v, a, lse, tq, tk, tv, to_ = saved
         inner, H = self.inner, self.heads
-        da, uo = linear_bwd_data(ctx, self.o, dout)
-        linear_bwd_lora(ctx, self.o, a, to_, dout, uo)
-        base_bwd_weight(ctx, self.o, a, dout)
+        da = linear_bwd(ctx, self.o, a, to_, dout)
         delta = torch.empty_like(lse)
         want_kv = self.is_self or self.need_kv_grad
         grouped = self.group is not None and ctx.dtype == torch.bfloat16
@@ -608,10 +621,9 @@ class AttnE:
                 dxn, _ = linear_bwd_data(ctx, self.fused_qkv, dqkv, accum=accum_xn)
                 return dxn
             if grouped:
-                dxn, u = self._group_bwd(ctx, dqkv, True, accum=accum_xn)
-                r = self.group.r
-                for i, (L, d, t_) in enumerate(((self.q, dq, tq), (self.k, dk, tk), (self.v, dv, tv))):
-                    linear_bwd_lora(ctx, L, xn, t_, d, u[:, i * r:(i + 1) * r])
+                dxn, u = group_bwd(ctx, self.group, dqkv, accum=accum_xn)
+                for L, d, t_, u_ in zip((self.q, self.k, self.v), (dq, dk, dv), (tq, tk, tv), self.group.split(u)):
+                    linear_bwd_lora(ctx, L, xn, t_, d, u_)
                     base_bwd_weight(ctx, L, xn, d)
                 return dxn
             dxn, uq = linear_bwd_data(ctx, self.q, dq, accum=accum_xn)
@@ -623,21 +635,16 @@ class AttnE:
             for L, d in ((self.q, dq), (self.k, dk), (self.v, dv)):
                 base_bwd_weight(ctx, L, xn, d)
             return dxn
-        dxn, uq = linear_bwd_data(ctx, self.q, dq, accum=accum_xn)
-        linear_bwd_lora(ctx, self.q, xn, tq, dq, uq)
-        base_bwd_weight(ctx, self.q, xn, dq)
-        if want_kv and self.k.r and dkv is not None:
-            _, u = self._group_bwd(ctx, dkv, False)
-            r = self.group.r
-            linear_bwd_lora(ctx, self.k, c, tk, dk, u[:, :r])
-            linear_bwd_lora(ctx, self.v, c, tv, dv, u[:, r:])
-        elif want_kv and self.k.r:
-            # context is an input (no data gradient needed), only the LoRA factors of to_k / to_v train
-            uk = ctx.new(B * Nkv, self.k.r); hip.gemm(dk, self.k.Bt, uk)
-            linear_bwd_lora(ctx, self.k, c, tk, dk, uk)
-            uv = ctx.new(B * Nkv, self.v.r); hip.gemm(dv, self.v.Bt, uv)
-            linear_bwd_lora(ctx, self.v, c, tv, dv, uv)
+        dxn = linear_bwd(ctx, self.q, xn, tq, dq, accum=accum_xn)
         if want_kv:
+            # the context is an input (no data gradient needed): only u = dy B for the LoRA factors of to_k / to_v
+            if dkv is not None:
+                uk, uv = self.group.split(group_bwd(ctx, self.group, dkv, need_dx=False)[1])
+                linear_bwd_lora(ctx, self.k, c, tk, dk, uk)
+                linear_bwd_lora(ctx, self.v, c, tv, dv, uv)
+            else:
+                linear_bwd_lora(ctx, self.k, c, tk, dk, lora_up_bwd(ctx, self.k, dk))
+                linear_bwd_lora(ctx, self.v, c, tv, dv, lora_up_bwd(ctx, self.v, dv))
             base_bwd_weight(ctx, self.k, c, dk)
             base_bwd_weight(ctx, self.v, c, dv)
         return dxn
@@ -671,33 +678,21 @@ class SpatialTransformerE:
         h2, sv2 = self.attn2.fwd(ctx, n2, c, B, N, Nkv, residual=h1, kv_cache=kv_cache, ln=l2, ip=ip)
         L = self.ff_proj
         xs_geglu = (not ctx.record and ctx.dtype == torch.bfloat16 and L.N % 64 == 0
-                    and hip.xs_geglu_ok(M, L.K, 0 if L.Wm is not None else L.r))
+                    and hip.xs_geglu_ok(M, L.K, 0 if folded(ctx, L) else L.r))
         tile_geglu = not xs_geglu and not ctx.record and L.geglu_ok()
         n3, s3, l3 = self.ln3.feed(ctx, h2, not tile_geglu and ln_prologue_ok(
             ctx, M, L.N, L.K, input_live(ctx, L), hip.ACT_GEGLU_SPLIT if xs_geglu else hip.ACT_NONE))
+        p = None
         if xs_geglu:
-            # the same fusion on the x-stationary kernel (csrc/gemm_xs.hip): W's rows in their natural [value | gate] order
-            tp = None
-            if L.r and L.Wm is None:
-                tp = ctx.new(B * N, L.r)
-                hip.gemm(n3, L.A, tp)
-            gg = ctx.new(B * N, 4 * self.C)
-            hip.gemm(n3, L.W if L.Wm is None else L.Wm, gg, a2=tp, w2=L.B if tp is not None else None, bias=L.bias,
-                     act=hip.ACT_GEGLU_SPLIT, N=L.N, ln=l3)
-            p = None
+            # no backward will need the 8C-wide pre-activation: value * gelu(gate) [M, 4C] is formed in the projection's epilogue
+            # (half the output bytes, no separate GEGLU pass) -- on the x-stationary kernel (csrc/gemm_xs.hip), which takes
+            # W's rows in their natural [value | gate] order
+            gg, tp = linear_fwd(ctx, L, n3, act=hip.ACT_GEGLU_SPLIT, ln=l3)
         elif tile_geglu:
-            # no backward will need the 8C-wide pre-activation: value * gelu(gate) is formed in the projection's
-            # epilogue (half the output bytes, no separate GEGLU pass)
-            Wg, bg, Bg = L.geglu_pack()
-            tp = None
-            if Bg is not None:
-                tp = ctx.new(B * N, L.r)
-                hip.gemm(n3, L.A, tp)
-            gg = ctx.new(B * N, 4 * self.C)
-            hip.gemm(n3, Wg, gg, a2=tp, w2=Bg, bias=bg, act=hip.ACT_GEGLU, N=L.N)
-            p = None
+            # the same fusion on the tile kernels: rows permuted so that every tile holds values next to their gates
+            gg, tp = linear_fwd(ctx, L, n3, act=hip.ACT_GEGLU, pack=L.geglu_pack())
         else:
-            p, tp = linear_fwd(ctx, self.ff_proj, n3, ln=l3)         # [M, 8C]
+            p, tp = linear_fwd(ctx, L, n3, ln=l3)                    # [M, 8C]
             gg = ctx.new(B * N, 4 * self.C)
             hip.geglu_fwd(p, gg)
         h3, tf = linear_fwd(ctx, self.ff_out, gg, residual=h2)
@@ -711,15 +706,11 @@ class SpatialTransformerE:
         base_bwd_weight(ctx, self.proj_out, h3, dout)
         dh, _ = linear_bwd_data(ctx, self.proj_out, dout)           # d h3 ; (x_in residual: + dout at the end)
         # feed-forward
-        dgg, uf = linear_bwd_data(ctx, self.ff_out, dh)
-        linear_bwd_lora(ctx, self.ff_out, gg, tf, dh, uf)
-        base_bwd_weight(ctx, self.ff_out, gg, dh)
+        dgg = linear_bwd(ctx, self.ff_out, gg, tf, dh)
         dp = ctx.new(B * N, 8 * self.C)
         hip.geglu_bwd(p, dgg, dp)
         del dgg
-        dn3, up = linear_bwd_data(ctx, self.ff_proj, dp)
-        linear_bwd_lora(ctx, self.ff_proj, n3, tp, dp, up)
-        base_bwd_weight(ctx, self.ff_proj, n3, dp)
+        dn3 = linear_bwd(ctx, self.ff_proj, n3, tp, dp)
         del dp
         dh = self.ln3.bwd(ctx, h2, dn3, s3, accum=dh)                # d h2
         ctx.drop_transposes()

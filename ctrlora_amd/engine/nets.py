@@ -26,7 +26,7 @@ import torch
 
 from .. import hip
 from .blocks import (AttnE, Ctx, ResBlockE, SpatialTransformerE, base_bwd_weight, conv3_bwd_data, conv3_bwd_weight,
-                     conv3_fwd, dense_bwd_weight, group_fwd, linear_bwd_data, linear_bwd_lora, linear_fwd)
+                     conv3_fwd, dense_bwd_weight, group_bwd, group_fwd, linear_bwd, linear_bwd_lora, linear_fwd, lora_up_bwd)
 from .packing import Conv3W, LinearW, LoraGroup, NormW, TrainableSet, rup
 
 
@@ -363,13 +363,9 @@ class _TimeEmbed:
     def bwd(self, ctx: Ctx, dsemb, saved):
         temb, te0, t0, h, emb, t2 = saved
         demb = ctx.new(*emb.shape); hip.silu_bwd(emb, dsemb, demb)
-        dh, u2 = linear_bwd_data(ctx, self.l2, demb)
-        linear_bwd_lora(ctx, self.l2, h, t2, demb, u2)
-        base_bwd_weight(ctx, self.l2, h, demb)
+        dh = linear_bwd(ctx, self.l2, h, t2, demb)
         dte0 = ctx.new(*te0.shape); hip.silu_bwd(te0, dh, dte0)
-        if self.l0.r:
-            u0 = ctx.new(dte0.shape[0], self.l0.r); hip.gemm(dte0, self.l0.Bt, u0)
-            linear_bwd_lora(ctx, self.l0, temb, t0, dte0, u0)
+        linear_bwd_lora(ctx, self.l0, temb, t0, dte0, lora_up_bwd(ctx, self.l0, dte0))      # (the timestep needs no gradient)
         base_bwd_weight(ctx, self.l0, temb, dte0)
         ctx.drop_transposes()
 
@@ -608,9 +604,8 @@ class ControlNetE:
             for grp, ls in self.emb_groups:
                 y, tt = group_fwd(ctx, grp, semb)
                 emb_tt.append(tt)
-                for i, l in enumerate(ls):
-                    env.emb_pre[id(l)] = (y[:, i * grp.N:(i + 1) * grp.N],
-                                          None if tt is None else tt[:, i * grp.r:(i + 1) * grp.r])
+                for l, y_, t_ in zip(ls, grp.split(y), grp.split(tt)):
+                    env.emb_pre[id(l)] = (y_, t_)
         h = hint_tok
         saved, hs, dims = [], [], []
         for k, layers in enumerate(self.blocks):
@@ -670,16 +665,9 @@ class ControlNetE:
         for (grp, ls), tt in zip(self.emb_groups, emb_tt):
             o0 = ls[0].de_off
             de_g = de[:, o0:o0 + grp.G * grp.N]
-            u = ctx.new(B, grp.G * grp.r)
-            if grp.r % 64 == 0:
-                hip.gemm(de_g, grp.Bt, u, k1=grp.N, a1_group_n=grp.r)
-            else:                                 # rank below the narrowest tile: one small product per member (as AttnE._group_bwd)
-                for i, l in enumerate(ls):
-                    hip.gemm(de_g[:, i * grp.N:(i + 1) * grp.N], l.blk.emb.Bt, u[:, i * grp.r:(i + 1) * grp.r])
-            hip.gemm(de_g, grp.Wt, env.dsemb, a2=u, w2=grp.At, residual=env.dsemb, beta=1.0)
-            for i, l in enumerate(ls):
-                linear_bwd_lora(ctx, l.blk.emb, semb, tt[:, i * grp.r:(i + 1) * grp.r], de_g[:, i * grp.N:(i + 1) * grp.N],
-                                u[:, i * grp.r:(i + 1) * grp.r])
+            _, u = group_bwd(ctx, grp, de_g, out=env.dsemb, accum=env.dsemb)
+            for L, t_, d, u_ in zip(grp.members, grp.split(tt), grp.split(de_g), grp.split(u)):
+                linear_bwd_lora(ctx, L, semb, t_, d, u_)
 
     def _done(self, ctx, span):
         """End of a backward stage: its queued weight gradients go out as one grouped launch, and once they are

@@ -253,6 +253,14 @@ class LoraGroup:
             L.B, L.Bt = self.B[g * N:(g + 1) * N], self.Bt[g * r:(g + 1) * r]
             L.group = self
 
+    def split(self, y):
+        """The members' column blocks of a side-by-side tensor: [M, G N] (outputs, their gradients) or [M, G r] (t = x A^T,
+        u = dy B).  None (a folded pass has no t) -> G Nones."""
+        if y is None:
+            return [None] * self.G
+        w = y.shape[1] // self.G
+        return [y[:, g * w:(g + 1) * w] for g in range(self.G)]
+
     def enable_merge(self):
         """Inference executors (W + B A folded): the members' merged weights live side by side -> ONE product for the group."""
         if self.Wm is None:
