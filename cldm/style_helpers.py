@@ -21,6 +21,9 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
+from ctrlora_amd.engine import clip_text, vit
+from ctrlora_amd.engine.clip_common import ExecutorHost
+
 IP_SCALE_TARGETS = {
     # every IPCrossAttention of the SD1.5 UNet
     "Load original IP-Adapter": ["input_blocks.1.1", "input_blocks.2.1", "input_blocks.4.1", "input_blocks.5.1",
@@ -76,30 +79,37 @@ VIT_H_14 = dict(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, 
                 image_size=224, patch_size=14, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=1024)
 
 
-def _vision_config(config):
-    from transformers import CLIPVisionConfig
+def _hf_config(cls, default: dict, sub_key: str, config):
+    """config as a `cls` (CLIPVisionConfig / CLIPTextConfig): None is `default`; a model directory gives its config.json
+    only (the `sub_key` entry where the file is a whole CLIPConfig)."""
     if config is None:
-        return CLIPVisionConfig(**VIT_H_14)
-    if isinstance(config, CLIPVisionConfig):
+        return cls(**default)
+    if isinstance(config, cls):
         return config
     if isinstance(config, dict):
-        return CLIPVisionConfig(**config)
-    if isinstance(config, (str, os.PathLike)) and os.path.isdir(config):       # an image_encoder/ directory: config.json only
+        return cls(**config)
+    if isinstance(config, (str, os.PathLike)) and os.path.isdir(config):
         import json
         with open(os.path.join(config, "config.json")) as f:
             d = json.load(f)
-        d = d.get("vision_config", d)
-        known = CLIPVisionConfig().to_dict()
-        return CLIPVisionConfig(**{k: v for k, v in d.items() if k in known and k not in ("model_type", "transformers_version")})
-    raise TypeError(f"config: a CLIPVisionConfig, a dict or a directory with config.json, not {type(config).__name__}")
+        d = d.get(sub_key, d)
+        known = cls().to_dict()
+        return cls(**{k: v for k, v in d.items() if k in known and k not in ("model_type", "transformers_version")})
+    raise TypeError(f"config: a {cls.__name__}, a dict or a directory with config.json, not {type(config).__name__}")
 
 
-class CLIPVisionEncoder(nn.Module):
+def _vision_config(config):
+    from transformers import CLIPVisionConfig
+    return _hf_config(CLIPVisionConfig, VIT_H_14, "vision_config", config)
+
+
+class CLIPVisionEncoder(ExecutorHost, nn.Module):
     """CLIPVisionModelWithProjection under HF's own state-dict keys (`vision_model.*`, `visual_projection.weight`), so an
     IP-Adapter image_encoder/ checkpoint loads with strict=True.  Built from a config (default: ViT-H/14), never from a hub
     name: nothing is downloaded, the weights come from load_state_dict.  On a GPU under no_grad, with a config the executor
     covers (ctrlora_amd/engine/vit.py: check_config), forward runs on the HIP engine in `engine_dtype` (bf16 unless
     set_engine_dtype / CTRLORA_ENGINE_DTYPE says fp32); otherwise (CPU, autograd, other configs) it is the plain HF module."""
+    ENGINE_SLOT, ENGINE_CLASS = "_vit", vit.ClipVisionE
 
     def __init__(self, config=None):
         super().__init__()
@@ -108,45 +118,10 @@ class CLIPVisionEncoder(nn.Module):
         hf = CLIPVisionModelWithProjection(self.config).eval()
         self.vision_model, self.visual_projection = hf.vision_model, hf.visual_projection      # HF's keys, no extra prefix
         self.__dict__["_hf"] = hf                                                              # (not a registered child)
-        self.engine_dtype = None
-        self.use_engine = True
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
-
-    def set_engine_dtype(self, dtype):
-        self.engine_dtype = dtype
-        self.invalidate_engine()
-
-    def invalidate_engine(self):
-        self.__dict__.pop("_vit", None)
-
-    def _refresh_engine(self):
-        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
-        ex = self.__dict__.get("_vit")
-        if ex is not None:
-            if ex.device != next(self.parameters()).device:
-                self.invalidate_engine()
-            else:
-                ex.load(self.state_dict())
-
-    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
-        self.invalidate_engine()
-        return super()._apply(fn, *args, **kwargs)
-
-    def engine(self):
-        ex = self.__dict__.get("_vit")
-        if ex is None:
-            from ctrlora_amd.engine.vit import ClipVisionE
-            dtype = self.engine_dtype
-            if dtype is None:
-                env = os.environ.get("CTRLORA_ENGINE_DTYPE", "bf16").lower()
-                dtype = torch.float32 if env in ("f32", "fp32", "float32") else torch.bfloat16
-            ex = ClipVisionE(self.state_dict(), self.config, dtype, next(self.parameters()).device)
-            self.__dict__["_vit"] = ex
-        return ex
+        self._init_engine_host()
 
     def _on_engine(self, pixel_values):
-        from ctrlora_amd.engine.vit import supported
-        return (self.use_engine and pixel_values.is_cuda and not torch.is_grad_enabled() and supported(self.config)
+        return (self.use_engine and pixel_values.is_cuda and not torch.is_grad_enabled() and vit.supported(self.config)
                 and tuple(pixel_values.shape[1:]) == (self.config.num_channels, self.config.image_size, self.config.image_size))
 
     def forward(self, pixel_values, output_hidden_states=False):
@@ -170,28 +145,16 @@ VIT_H_14_TEXT = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096,
 
 def _text_config(config):
     from transformers import CLIPTextConfig
-    if config is None:
-        return CLIPTextConfig(**VIT_H_14_TEXT)
-    if isinstance(config, CLIPTextConfig):
-        return config
-    if isinstance(config, dict):
-        return CLIPTextConfig(**config)
-    if isinstance(config, (str, os.PathLike)) and os.path.isdir(config):       # a model directory: config.json only
-        import json
-        with open(os.path.join(config, "config.json")) as f:
-            d = json.load(f)
-        d = d.get("text_config", d)
-        known = CLIPTextConfig().to_dict()
-        return CLIPTextConfig(**{k: v for k, v in d.items() if k in known and k not in ("model_type", "transformers_version")})
-    raise TypeError(f"config: a CLIPTextConfig, a dict or a directory with config.json, not {type(config).__name__}")
+    return _hf_config(CLIPTextConfig, VIT_H_14_TEXT, "text_config", config)
 
 
-class CLIPTextEncoder(nn.Module):
+class CLIPTextEncoder(ExecutorHost, nn.Module):
     """CLIPTextModelWithProjection under HF's own state-dict keys (`text_model.*`, `text_projection.weight`).  Built from a
     config (default: the ViT-H/14 text tower), never from a hub name: nothing is downloaded, the weights come from
     load_state_dict.  On a GPU under no_grad, with a config the executor covers (ctrlora_amd/engine/clip_text.py: check_config)
     and no padding mask, forward runs on the HIP engine in `engine_dtype` (bf16 unless set_engine_dtype / CTRLORA_ENGINE_DTYPE
     says fp32); otherwise (CPU, autograd, other configs, use_engine = False) it is the plain HF module."""
+    ENGINE_SLOT, ENGINE_CLASS = "_txt", clip_text.ClipTextE
 
     def __init__(self, config=None):
         super().__init__()
@@ -200,45 +163,10 @@ class CLIPTextEncoder(nn.Module):
         hf = CLIPTextModelWithProjection(self.config).eval()
         self.text_model, self.text_projection = hf.text_model, hf.text_projection              # HF's keys, no extra prefix
         self.__dict__["_hf"] = hf                                                              # (not a registered child)
-        self.engine_dtype = None
-        self.use_engine = True
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
-
-    def set_engine_dtype(self, dtype):
-        self.engine_dtype = dtype
-        self.invalidate_engine()
-
-    def invalidate_engine(self):
-        self.__dict__.pop("_txt", None)
-
-    def _refresh_engine(self):
-        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
-        ex = self.__dict__.get("_txt")
-        if ex is not None:
-            if ex.device != next(self.parameters()).device:
-                self.invalidate_engine()
-            else:
-                ex.load(self.state_dict())
-
-    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
-        self.invalidate_engine()
-        return super()._apply(fn, *args, **kwargs)
-
-    def engine(self):
-        ex = self.__dict__.get("_txt")
-        if ex is None:
-            from ctrlora_amd.engine.clip_text import ClipTextE
-            dtype = self.engine_dtype
-            if dtype is None:
-                env = os.environ.get("CTRLORA_ENGINE_DTYPE", "bf16").lower()
-                dtype = torch.float32 if env in ("f32", "fp32", "float32") else torch.bfloat16
-            ex = ClipTextE(self.state_dict(), self.config, dtype, next(self.parameters()).device)
-            self.__dict__["_txt"] = ex
-        return ex
+        self._init_engine_host()
 
     def _on_engine(self, input_ids, attention_mask):
-        from ctrlora_amd.engine.clip_text import supported
-        return (self.use_engine and input_ids.is_cuda and not torch.is_grad_enabled() and supported(self.config, attention_mask)
+        return (self.use_engine and input_ids.is_cuda and not torch.is_grad_enabled() and clip_text.supported(self.config, attention_mask)
                 and input_ids.dim() == 2 and 1 <= input_ids.shape[1] <= self.config.max_position_embeddings)
 
     def forward(self, input_ids, attention_mask=None):

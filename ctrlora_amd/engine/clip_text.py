@@ -1,13 +1,13 @@
 """CLIP text encoder (CLIPTextModel / CLIPTextModelWithProjection in HF layout: ViT-L/14 text for the prompt, ViT-H/14 text for the
-style app's negative content prompt) on the HIP kernels.  The sibling of vit.py.
+style app's negative content prompt) on the HIP kernels.  The sibling of vit.py: what the two share is in clip_common.py.
 
 Where the reference calls it: FrozenCLIPEmbedder encodes every prompt (ldm/modules/encoders/modules.py:88-131); the style app
 encodes the negative content prompt with CLIPTextModelWithProjection (app/gradio_ctrlora_style_transfer.py:395-403).  Modules
 restated (behaviour, not code; transformers/models/clip/modeling_clip.py):
 
   CLIPTextEmbeddings   token_embedding(input_ids) + position_embedding                      (cl_clip_text_embed)
-  CLIPEncoderLayer     pre-LN: x + out_proj(attn(LN1 x)); x + fc2(act(fc1(LN2 x)))
-  CLIPAttention        causal: softmax_{j <= i}(q k^T d^-1/2) v, q | k | v as ONE product     (cl_attention_causal_fwd, d_head 64)
+  CLIPEncoderLayer     the layer both towers walk: clip_common.py (encoder_layer, pack_layers)
+  CLIPAttention        causal: softmax_{j <= i}(q k^T d^-1/2) v                              (cl_attention_causal_fwd, d_head 64)
   CLIPMLP              "gelu": the exact GELU epilogue (cl_gemm act 4).  "quick_gelu", x sigmoid(1.702 x), is the SiLU epilogue
                        by algebra: quick_gelu(x) = silu(1.702 x) / 1.702 -- fc1's weight and bias are packed multiplied by
                        1.702 (in fp32, before the cast to the engine dtype) and the product runs with act = SiLU,
@@ -32,7 +32,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import hip
-from .vit import K_GRAIN
+from . import clip_common as cc
 
 D_HEAD = 64                                  # csrc/attention_causal.hip
 MAX_TOKENS = 128
@@ -56,27 +56,17 @@ def check_config(config, attention_mask: Optional[torch.Tensor] = None) -> dict:
     c = config_fields(config)
     if c["hidden_act"] not in ("gelu", "quick_gelu"):
         raise ValueError(f"hidden_act = {c['hidden_act']!r}: the executor has the exact GELU and (through SiLU) the quick_gelu epilogue only")
-    D, H = c["hidden_size"], c["num_attention_heads"]
-    if D % H or D // H != D_HEAD:
-        raise ValueError(f"num_attention_heads = {H} with hidden_size = {D}: d_head {D / H:g} is not {D_HEAD} (the causal kernel's)")
+    cc.check_d_head(c, (D_HEAD,), f"{D_HEAD} (the causal kernel's)")
     if not 1 <= c["max_position_embeddings"] <= MAX_TOKENS:
         raise ValueError(f"max_position_embeddings = {c['max_position_embeddings']}: the causal kernel takes 1 .. {MAX_TOKENS} tokens")
-    for k in ("hidden_size", "intermediate_size"):
-        if c[k] % K_GRAIN:
-            raise ValueError(f"{k} = {c[k]} is not a multiple of {K_GRAIN} (K granularity of the products)")
-    if c["projection_dim"] % 8:
-        raise ValueError(f"projection_dim = {c['projection_dim']} is not a multiple of 8")
+    cc.check_widths(c)
     if attention_mask is not None and not bool((attention_mask == 1).all()):
         raise ValueError("attention_mask is not all ones: the causal kernel has no padding mask")
     return c
 
 
 def supported(config, attention_mask: Optional[torch.Tensor] = None) -> bool:
-    try:
-        check_config(config, attention_mask)
-        return True
-    except ValueError:
-        return False
+    return cc.supported(check_config, config, attention_mask)
 
 
 def state_keys(config, prefix: str = "text_model.", projection: bool = False) -> List[str]:
@@ -85,11 +75,7 @@ def state_keys(config, prefix: str = "text_model.", projection: bool = False) ->
     text_projection.weight."""
     c = config_fields(config)
     keys = [prefix + "embeddings.token_embedding.weight", prefix + "embeddings.position_embedding.weight"]
-    for i in range(c["num_hidden_layers"]):
-        p = f"{prefix}encoder.layers.{i}."
-        for m in ("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj", "self_attn.out_proj", "layer_norm1", "mlp.fc1", "mlp.fc2",
-                  "layer_norm2"):
-            keys += [p + m + ".weight", p + m + ".bias"]
+    keys += cc.layer_state_keys(prefix, c["num_hidden_layers"])
     keys += [prefix + "final_layer_norm.weight", prefix + "final_layer_norm.bias"]
     return keys + (["text_projection.weight"] if projection else [])
 
@@ -110,19 +96,10 @@ def pack_clip_text(sd: Dict[str, torch.Tensor], config) -> dict:
     t = _prefix(sd)
     s1 = QUICK_GELU if c["hidden_act"] == "quick_gelu" else 1.0
     out = dict(tok=f(t + "embeddings.token_embedding.weight"), pos=f(t + "embeddings.position_embedding.weight"),
-               fin_g=f(t + "final_layer_norm.weight"), fin_b=f(t + "final_layer_norm.bias"), layers=[])
+               fin_g=f(t + "final_layer_norm.weight"), fin_b=f(t + "final_layer_norm.bias"),
+               layers=cc.pack_layers(sd, t, c["num_hidden_layers"], f, fc1_scale=s1))
     if "text_projection.weight" in sd:
         out["proj_w"] = f("text_projection.weight")
-    for i in range(c["num_hidden_layers"]):
-        p = f"{t}encoder.layers.{i}."
-        a = p + "self_attn."
-        out["layers"].append(dict(
-            ln1_g=f(p + "layer_norm1.weight"), ln1_b=f(p + "layer_norm1.bias"),
-            qkv_w=torch.cat([f(a + n + "_proj.weight") for n in "qkv"], 0), qkv_b=torch.cat([f(a + n + "_proj.bias") for n in "qkv"], 0),
-            o_w=f(a + "out_proj.weight"), o_b=f(a + "out_proj.bias"),
-            ln2_g=f(p + "layer_norm2.weight"), ln2_b=f(p + "layer_norm2.bias"),
-            fc1_w=f(p + "mlp.fc1.weight") * s1, fc1_b=f(p + "mlp.fc1.bias") * s1,
-            fc2_w=f(p + "mlp.fc2.weight"), fc2_b=f(p + "mlp.fc2.bias")))
     return out
 
 
@@ -183,43 +160,25 @@ def clip_text_forward_torch(packed: dict, ids: torch.Tensor, config, want=("last
 _WEIGHTS = ("proj_w", "qkv_w", "o_w", "fc1_w", "fc2_w")       # engine dtype; everything else stays fp32
 
 
-class ClipTextE:
+class ClipTextE(cc.ClipExecutor):
     """CLIPTextModel(.WithProjection).forward: input_ids [B, N] int64 -> the outputs named in `want`."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config, dtype, device=None):
-        self.cfg = check_config(config)                 # (before anything touches the GPU: the refusals need none)
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"dtype = {dtype}: the engine stores bf16 or fp32")
-        hip.lib()
+        super().__init__(check_config(config), state_dict, dtype, device)
         c = self.cfg
-        self.dtype = dtype
-        self.device = torch.device(device if device is not None else next(iter(state_dict.values())).device)
-        self.D, self.H, self.F, self.L = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"], c["num_hidden_layers"]
         self.scale = float(D_HEAD) ** -0.5
-        self.eps = float(c["layer_norm_eps"])
         self.quick = c["hidden_act"] == "quick_gelu"
-        self.w = self._to_device(pack_clip_text(state_dict, c))
+        self.w = self._to_device(self.pack(state_dict), _WEIGHTS)
         assert tuple(self.w["pos"].shape) == (c["max_position_embeddings"], self.D) and self.w["tok"].shape[0] == c["vocab_size"]
-        self._buf: Dict[tuple, dict] = {}
         self.forwards = 0                                # forwards that ran on the engine (what the tests read)
 
-    def _to_device(self, packed: dict) -> dict:
-        mv = lambda k, t: t.to(device=self.device, dtype=self.dtype if k in _WEIGHTS else torch.float32).contiguous()
-        out = {k: mv(k, t) for k, t in packed.items() if k != "layers"}
-        out["layers"] = [{k: mv(k, t) for k, t in lay.items()} for lay in packed["layers"]]
-        return out
+    def pack(self, state_dict: Dict[str, torch.Tensor]) -> dict:
+        return pack_clip_text(state_dict, self.cfg)
 
     def load(self, state_dict: Dict[str, torch.Tensor]):
-        """Refresh the packed weights in place (the address rule of engine/packing.py: a captured graph keeps replaying them)."""
-        new = pack_clip_text(state_dict, self.cfg)
-        if set(new) != set(self.w):
+        if ("text_projection.weight" in state_dict) != ("proj_w" in self.w):
             raise ValueError("the state dict gains or loses text_projection.weight: build a new executor")
-        for k, t in new.items():
-            if k != "layers":
-                self.w[k].copy_(t)
-        for old, lay in zip(self.w["layers"], new["layers"]):
-            for k, t in lay.items():
-                old[k].copy_(t)
+        super().load(state_dict)
 
     def _buffers(self, B: int, N: int) -> dict:
         b = self._buf.get((B, N))
@@ -257,39 +216,31 @@ class ClipTextE:
         D, H, w, b = self.D, self.H, self.w, self._buffers(B, N)
         ids = b["ids"]
         ids.copy_(input_ids)
-        x, qkv, a, m, mid = b["x"], b["qkv"], b["a"], b["m"], b["h"][2]
+        x, qkv, a, m = b["x"], b["qkv"], b["a"], b["m"]
         mixed = self.dtype != torch.float32
         act, alpha = (hip.ACT_SILU, 1.0 / QUICK_GELU) if self.quick else (hip.ACT_GELU, 1.0)
 
         def norm(src, g, bt):              # LayerNorm of the fp32 stream -> x in the engine dtype
             if mixed:
-                hip.layernorm_fwd(src, b["x32"], g, bt, self.eps)
-                hip.pack2d(b["x32"], x)
-            else:
-                hip.layernorm_fwd(src, x, g, bt, self.eps)
+                return hip.pack2d(hip.layernorm_fwd(src, b["x32"], g, bt, self.eps), x)
+            return hip.layernorm_fwd(src, x, g, bt, self.eps)
+
+        attend = lambda qkv: hip.attention_causal(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, H, N, D_HEAD, self.scale)
+        layer = lambda lay, src, mid, out: cc.encoder_layer(lay, src, mid, out, qkv, m, norm=norm, attend=attend, act=act, alpha=alpha,
+                                                            atomic=mixed)
 
         cur = b["hid"] if k == 0 and not mixed else b["h"][0]
         hip.clip_text_embed(ids, w["tok"], w["pos"], cur)
         if mixed and k == 0:
             hip.axpby(cur, b["hid"], 1.0, 0.0)
         for i, lay in enumerate(w["layers"][:nlayers]):
-            norm(cur, lay["ln1_g"], lay["ln1_b"])
-            hip.gemm(x, lay["qkv_w"], qkv, bias=lay["qkv_b"])
-            hip.attention_causal(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, H, N, D_HEAD, self.scale)
             if mixed:                      # the stream is updated in place: cur += branch, twice
-                hip.gemm(a, lay["o_w"], cur, bias=lay["o_b"], atomic=True)
-                norm(cur, lay["ln2_g"], lay["ln2_b"])
-                hip.gemm(x, lay["fc1_w"], m, bias=lay["fc1_b"], act=act, alpha=alpha)
-                hip.gemm(m, lay["fc2_w"], cur, bias=lay["fc2_b"], atomic=True)
+                layer(lay, cur, cur, cur)
                 if k == i + 1:
                     hip.axpby(cur, b["hid"], 1.0, 0.0)
-                continue
-            out = b["hid"] if k == i + 1 else (b["h"][1] if cur is b["h"][0] else b["h"][0])
-            hip.gemm(a, lay["o_w"], mid, bias=lay["o_b"], residual=cur, beta=1.0)
-            norm(mid, lay["ln2_g"], lay["ln2_b"])
-            hip.gemm(x, lay["fc1_w"], m, bias=lay["fc1_b"], act=act, alpha=alpha)
-            hip.gemm(m, lay["fc2_w"], out, bias=lay["fc2_b"], residual=mid, beta=1.0)
-            cur = out
+            else:
+                out = b["hid"] if k == i + 1 else (b["h"][1] if cur is b["h"][0] else b["h"][0])
+                cur = layer(lay, cur, b["h"][2], out)
         res = {}
         if k is not None:
             res["hidden_state"] = b["hid"].view(B, N, D)

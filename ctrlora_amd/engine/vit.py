@@ -7,9 +7,9 @@ ImageProjModel).  Modules restated (behaviour, not code; transformers/models/cli
   CLIPVisionEmbeddings  :138-218  patch_embedding (stride-P P x P conv, no bias) as patch rows x one linear product,
                                   class embedding in front, + position_embedding (cl_vit_patch_rows, cl_vit_tokens)
   CLIPVisionModel       :594-656  pre_layrnorm (the upstream spelling) -> encoder -> post_layernorm of the class rows
-  CLIPEncoderLayer      :353-384  pre-LN: x + out_proj(attn(LN1 x)); x + fc2(gelu(fc1(LN2 x)))
-  CLIPAttention         :280-335  no mask: softmax(q k^T d^-1/2) v, q | k | v as ONE product (q pre-scaled in bf16)
-  CLIPMLP               :338-350  fc1 with the exact GELU in the product's epilogue (cl_gemm act 4), fc2 with the residual
+  CLIPEncoderLayer, CLIPAttention, CLIPMLP      the layer both towers walk: clip_common.py (encoder_layer, pack_layers).  Here:
+                                  no mask (cl_attention_fwd*, q pre-scaled by the qkv product in bf16), the exact GELU in fc1's
+                                  epilogue (cl_gemm act 4), the stream in the engine dtype over three rotating buffers
   CLIPVisionModelWithProjection :898-957  visual_projection (no bias) of the pooled class rows -> image_embeds
 
 Inference only.  Activations are token-major [B*T, D] in the engine dtype; every buffer is allocated once per batch size and
@@ -23,10 +23,11 @@ from typing import Dict, List
 import torch
 
 from .. import hip
+from . import clip_common as cc
+from .clip_common import K_GRAIN
 from .packing import rup
 
 ATTN_D_HEADS = (8, 16, 32, 40, 80, 160)      # csrc/attention_fwd.hip: dispatch_dh, csrc/attention_tr.hip: attn_fwd_tr
-K_GRAIN = 32                                 # cl_gemm's K granularity in bf16 (16 in fp32): 3 * 14 * 14 = 588 -> 608
 
 _FIELDS = ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "num_channels", "image_size",
            "patch_size", "projection_dim", "layer_norm_eps", "hidden_act")
@@ -45,23 +46,13 @@ def check_config(config) -> dict:
         raise ValueError(f"hidden_act = {c['hidden_act']!r}: the executor has the exact (erf) GELU epilogue only")
     if c["image_size"] % c["patch_size"]:
         raise ValueError(f"image_size = {c['image_size']} is not a multiple of patch_size = {c['patch_size']}")
-    D, H = c["hidden_size"], c["num_attention_heads"]
-    if D % H or D // H not in ATTN_D_HEADS:
-        raise ValueError(f"num_attention_heads = {H} with hidden_size = {D}: d_head {D / H:g} is not one of {ATTN_D_HEADS}")
-    for k in ("hidden_size", "intermediate_size"):
-        if c[k] % K_GRAIN:
-            raise ValueError(f"{k} = {c[k]} is not a multiple of {K_GRAIN} (K granularity of the products)")
-    if c["projection_dim"] % 8:
-        raise ValueError(f"projection_dim = {c['projection_dim']} is not a multiple of 8")
+    cc.check_d_head(c, ATTN_D_HEADS, f"one of {ATTN_D_HEADS}")
+    cc.check_widths(c)
     return c
 
 
 def supported(config) -> bool:
-    try:
-        check_config(config)
-        return True
-    except ValueError:
-        return False
+    return cc.supported(check_config, config)
 
 
 def state_keys(config) -> List[str]:
@@ -70,11 +61,7 @@ def state_keys(config) -> List[str]:
     v = "vision_model."
     keys = [v + "embeddings.class_embedding", v + "embeddings.patch_embedding.weight", v + "embeddings.position_embedding.weight",
             v + "pre_layrnorm.weight", v + "pre_layrnorm.bias"]
-    for i in range(c["num_hidden_layers"]):
-        p = f"{v}encoder.layers.{i}."
-        for m in ("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj", "self_attn.out_proj", "layer_norm1", "mlp.fc1", "mlp.fc2",
-                  "layer_norm2"):
-            keys += [p + m + ".weight", p + m + ".bias"]
+    keys += cc.layer_state_keys(v, c["num_hidden_layers"])
     return keys + [v + "post_layernorm.weight", v + "post_layernorm.bias", "visual_projection.weight"]
 
 
@@ -99,64 +86,33 @@ def pack_clip_vision(sd: Dict[str, torch.Tensor], config) -> dict:
     v = "vision_model."
     D, Kp = c["hidden_size"], patch_kpad(config)
     pw = f(v + "embeddings.patch_embedding.weight").reshape(D, -1)
-    out = dict(patch_w=torch.nn.functional.pad(pw, (0, Kp - pw.shape[1])), cls=f(v + "embeddings.class_embedding").reshape(D),
+    return dict(patch_w=torch.nn.functional.pad(pw, (0, Kp - pw.shape[1])), cls=f(v + "embeddings.class_embedding").reshape(D),
                pos=f(v + "embeddings.position_embedding.weight"), pre_g=f(v + "pre_layrnorm.weight"), pre_b=f(v + "pre_layrnorm.bias"),
                post_g=f(v + "post_layernorm.weight"), post_b=f(v + "post_layernorm.bias"), proj_w=f("visual_projection.weight"),
-               layers=[])
-    for i in range(c["num_hidden_layers"]):
-        p = f"{v}encoder.layers.{i}."
-        a = p + "self_attn."
-        out["layers"].append(dict(
-            ln1_g=f(p + "layer_norm1.weight"), ln1_b=f(p + "layer_norm1.bias"),
-            qkv_w=torch.cat([f(a + n + "_proj.weight") for n in "qkv"], 0), qkv_b=torch.cat([f(a + n + "_proj.bias") for n in "qkv"], 0),
-            o_w=f(a + "out_proj.weight"), o_b=f(a + "out_proj.bias"),
-            ln2_g=f(p + "layer_norm2.weight"), ln2_b=f(p + "layer_norm2.bias"),
-            fc1_w=f(p + "mlp.fc1.weight"), fc1_b=f(p + "mlp.fc1.bias"), fc2_w=f(p + "mlp.fc2.weight"), fc2_b=f(p + "mlp.fc2.bias")))
-    return out
+               layers=cc.pack_layers(sd, v, c["num_hidden_layers"], f))
 
 
 _WEIGHTS = ("patch_w", "proj_w", "qkv_w", "o_w", "fc1_w", "fc2_w")       # engine dtype; everything else stays fp32
 
 
-class ClipVisionE:
+class ClipVisionE(cc.ClipExecutor):
     """CLIPVisionModelWithProjection.forward: pixel_values (B, C, S, S) fp32 -> image_embeds (B, projection_dim) fp32."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config, dtype, device=None):
-        self.cfg = check_config(config)                 # (before anything touches the GPU: the refusals need none)
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"dtype = {dtype}: the engine stores bf16 or fp32")
-        hip.lib()
+        super().__init__(check_config(config), state_dict, dtype, device)
         c = self.cfg
-        self.dtype = dtype
-        self.device = torch.device(device if device is not None else next(iter(state_dict.values())).device)
-        self.D, self.H, self.F, self.L = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"], c["num_hidden_layers"]
         self.P, self.S, self.C = c["patch_size"], c["image_size"], c["num_channels"]
         self.T = (self.S // self.P) ** 2 + 1
         self.dh = self.D // self.H
         self.scale = float(self.dh) ** -0.5
-        self.eps = float(c["layer_norm_eps"])
         self.Kpad = patch_kpad(c)
         from .blocks import PRESCALE_Q
         self.prescaled = PRESCALE_Q and dtype == torch.bfloat16       # CL_ATTN_Q_PRESCALED: as the UNet's self-attentions
-        self.w = self._to_device(pack_clip_vision(state_dict, c))
+        self.w = self._to_device(self.pack(state_dict), _WEIGHTS)
         assert tuple(self.w["pos"].shape) == (self.T, self.D), (tuple(self.w["pos"].shape), self.T, self.D)
-        self._buf: Dict[int, dict] = {}
 
-    def _to_device(self, packed: dict) -> dict:
-        mv = lambda k, t: t.to(device=self.device, dtype=self.dtype if k in _WEIGHTS else torch.float32).contiguous()
-        out = {k: mv(k, t) for k, t in packed.items() if k != "layers"}
-        out["layers"] = [{k: mv(k, t) for k, t in lay.items()} for lay in packed["layers"]]
-        return out
-
-    def load(self, state_dict: Dict[str, torch.Tensor]):
-        """Refresh the packed weights in place (the address rule of engine/packing.py: a captured graph keeps replaying them)."""
-        new = pack_clip_vision(state_dict, self.cfg)
-        for k, t in new.items():
-            if k != "layers":
-                self.w[k].copy_(t)
-        for old, lay in zip(self.w["layers"], new["layers"]):
-            for k, t in lay.items():
-                old[k].copy_(t)
+    def pack(self, state_dict: Dict[str, torch.Tensor]) -> dict:
+        return pack_clip_vision(state_dict, self.cfg)
 
     def _buffers(self, B: int) -> dict:
         b = self._buf.get(B)
@@ -188,17 +144,13 @@ class ClipVisionE:
         hip.gemm(b["rows"], w["patch_w"], b["pe"])
         hip.vit_tokens(b["pe"], w["cls"], w["pos"], hB, B)
         hip.layernorm_fwd(hB, hA, w["pre_g"], w["pre_b"], self.eps)
-        qa = self.scale * 1.4426950408889634 if self.prescaled else 1.0
-        for i, lay in enumerate(w["layers"]):
-            out = hC if i == self.L - 1 else hA          # hA keeps the penultimate hidden state
-            hip.layernorm_fwd(hA, x, lay["ln1_g"], lay["ln1_b"], self.eps)
-            hip.gemm(x, lay["qkv_w"], qkv, bias=lay["qkv_b"], alpha=qa, alpha_n=D if self.prescaled else 0)
-            q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
-            hip.attention(q, k, v, a, None, B, H, T, T, self.dh, self.scale, q_prescaled=self.prescaled, vt=b.get("vt"))
-            hip.gemm(a, lay["o_w"], hB, bias=lay["o_b"], residual=hA, beta=1.0)
-            hip.layernorm_fwd(hB, x, lay["ln2_g"], lay["ln2_b"], self.eps)
-            hip.gemm(x, lay["fc1_w"], m, bias=lay["fc1_b"], act=hip.ACT_GELU)
-            hip.gemm(m, lay["fc2_w"], out, bias=lay["fc2_b"], residual=hB, beta=1.0)
+        qa, qn = (self.scale * 1.4426950408889634, D) if self.prescaled else (1.0, 0)
+        norm = lambda src, g, bt: hip.layernorm_fwd(src, x, g, bt, self.eps)
+        attend = lambda qkv: hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, None, B, H, T, T, self.dh, self.scale,
+                                           q_prescaled=self.prescaled, vt=b.get("vt"))
+        for i, lay in enumerate(w["layers"]):            # hA keeps the penultimate hidden state
+            cc.encoder_layer(lay, hA, hB, hC if i == self.L - 1 else hA, qkv, m, norm=norm, attend=attend, act=hip.ACT_GELU,
+                             qkv_alpha=qa, qkv_alpha_n=qn)
         last = hC if self.L > 0 else hA
         # post_layernorm of the class rows only (row b T of every sample), then visual_projection
         hip.layernorm_fwd(last.view(B, T * D)[:, :D], b["pooled"], w["post_g"], w["post_b"], self.eps)

@@ -7,6 +7,9 @@ build / bench environment, so construction never downloads; benchmarks feed a sy
 import torch
 import torch.nn as nn
 
+from ctrlora_amd.engine import clip_text
+from ctrlora_amd.engine.clip_common import ExecutorHost
+
 
 class AbstractEncoder(nn.Module):
     def encode(self, *args, **kwargs):
@@ -25,7 +28,7 @@ def _hash_tokens(texts, max_length, vocab=49408, bos=49406, eos=49407):
     return ids
 
 
-class FrozenCLIPEmbedder(AbstractEncoder):
+class FrozenCLIPEmbedder(ExecutorHost, AbstractEncoder):
     """CLIP ViT-L/14 text encoder through HF transformers (ldm/modules/encoders/modules.py:88-131).  The module tree
     (`transformer.text_model.*`, the keys an SD checkpoint carries under `cond_stage_model.`) is built from the model's
     CONFIG -- no download; pretrained weights are picked up from a local HF cache when one exists, otherwise they come
@@ -36,6 +39,7 @@ class FrozenCLIPEmbedder(AbstractEncoder):
     engine stays at about 1e-6 of the HF module's output.  use_engine = False (or the CPU, or another config) is the plain HF
     module.  The engine's `forwards` counter says which path ran."""
     LAYERS = ["last", "pooled", "hidden"]
+    ENGINE_SLOT, ENGINE_CLASS = "_txt", clip_text.ClipTextE
 
     def __init__(self, version="openai/clip-vit-large-patch14", device="cuda", max_length=77, freeze=True, layer="last",
                  layer_idx=None):
@@ -59,45 +63,16 @@ class FrozenCLIPEmbedder(AbstractEncoder):
         self.tokenizer = None
         if layer == "hidden":
             assert layer_idx is not None and 0 <= abs(layer_idx) <= 12
-        self.engine_dtype = torch.float32
-        self.use_engine = True
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_engine())
+        self._init_engine_host(torch.float32)
         if freeze:
             self.freeze()
 
-    def set_engine_dtype(self, dtype):
-        self.engine_dtype = dtype
-        self.invalidate_engine()
-
-    def invalidate_engine(self):
-        self.__dict__.pop("_txt", None)
-
-    def _refresh_engine(self):
-        """load_state_dict after the first forward: the executor's packed weights are refreshed in place."""
-        ex = self.__dict__.get("_txt")
-        if ex is not None:
-            if ex.device != next(self.transformer.parameters()).device:
-                self.invalidate_engine()
-            else:
-                ex.load(self.transformer.state_dict())
-
-    def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): the packed copies follow the parameters
-        self.invalidate_engine()
-        return super()._apply(fn, *args, **kwargs)
-
-    def engine(self):
-        ex = self.__dict__.get("_txt")
-        if ex is None:
-            from ctrlora_amd.engine.clip_text import ClipTextE
-            ex = ClipTextE(self.transformer.state_dict(), self.transformer.config, self.engine_dtype,
-                           next(self.transformer.parameters()).device)
-            self.__dict__["_txt"] = ex
-        return ex
+    def _engine_source(self):
+        return self.transformer
 
     def _on_engine(self, ids):
-        from ctrlora_amd.engine.clip_text import supported
         cfg = self.transformer.config
-        return (self.use_engine and next(self.transformer.parameters()).is_cuda and supported(cfg)
+        return (self.use_engine and next(self.transformer.parameters()).is_cuda and clip_text.supported(cfg)
                 and 1 <= ids.shape[1] <= cfg.max_position_embeddings)
 
     def freeze(self):
