@@ -1430,13 +1430,15 @@ int launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
     t_force_sk = 0;
     return rc;
   }
-  if (p.act == ACT_GEGLU_SPLIT || p.ln_gamma)   // natural-order GEGLU rows / LayerNorm prologue: the x-stationary kernel only (gemm_xs.hip)
-    return dtype == CL_BF16 ? launch_gemm_xs(p, stream, g_gemm_force_splitk) : CL_EINVAL;
+  // (the range checks come first: they are predicates on the case and hold for the two x-stationary-only forms below as for
+  // every other product)
   if (p.a1_group_n < 0 || p.a2_group_n < 0) return CL_EINVAL;
   if (p.alpha_n < 0 || p.alpha_n % 8 || p.alpha_n > p.N || (p.alpha_n && p.act == ACT_GEGLU)) return CL_EINVAL;
   if ((p.a1_group_n || p.a2_group_n) && p.mode != GEMM_LINEAR) return CL_EINVAL;
   if (p.a1_group_n && p.N % p.a1_group_n) return CL_EINVAL;
   if (p.a2_group_n && (p.N % p.a2_group_n || !p.K2)) return CL_EINVAL;
+  if (p.act == ACT_GEGLU_SPLIT || p.ln_gamma)   // natural-order GEGLU rows / LayerNorm prologue: the x-stationary kernel only (gemm_xs.hip)
+    return dtype == CL_BF16 ? launch_gemm_xs(p, stream, g_gemm_force_splitk) : CL_EINVAL;
   return dtype == CL_BF16 ? launch_t<bf16_t>(p, stream) : launch_t<float>(p, stream);
 }
 

@@ -110,9 +110,15 @@ __global__ __launch_bounds__(256, MINW) void gemm_xs_kernel(GemmParams p, int cp
   const int nob = min(cpw, (ncols - n_base) / 32);       // output blocks of this workgroup
   if (nob <= 0 || (int)blockIdx.x >= (p.M + 127) / 128) return;      // (past M: launch-tag workgroups, csrc/debug_hooks.h)
   const int nch = nob * CPB;                             // chunks (= loop iterations)
-  // rows past M repeat row M - 1: same operands, same results, the same bytes stored twice -- no predication anywhere, so the
-  // instruction counts the vmcnt arithmetic relies on are exact
+  // rows past M repeat row M - 1: same operands, same results, the same bytes stored twice -- no per-lane predication anywhere, so
+  // the instruction counts the vmcnt arithmetic relies on are exact
   const long row = min((long)blockIdx.x * 128 + wave * 32 + l31, (long)p.M - 1);
+  // ... with one exception, per WAVE: a wave of the residual form whose 32 rows all lie past M (M % 128 in 1 .. 96) holds copies of
+  // row M - 1 only and issues no stores.  In place (C == residual) it would otherwise load residual[M - 1] and store C[M - 1]
+  // beside the wave that owns the row, and nothing orders one wave's store against another wave's load of the same block: a late
+  // wave would read the updated row and store acc + beta (acc + beta r).  The row's owner stores it; copies inside the owner's wave
+  // are lanes of one load and one store instruction.  The wave's store count enters `allow` as spb (tests/test_xs_vmcnt_model.py).
+  const bool dupw = EPI == XS_RES && (long)blockIdx.x * 128 + wave * 32 >= (long)p.M;
 
   // ---- [x | t] rows of this wave -> registers (B operand: column = row l31 of the wave's block, k = 16 j + 8 hi .. + 7)
   u32x4_t xa[KS];
@@ -288,7 +294,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_xs_kernel(GemmParams p, int cp
       const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
       const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
       const u32x4_t w = {rx[0], ry[0], rx[1], ry[1]};
-      *reinterpret_cast<u32x4_t*>(yrow + b * 32 + 16 * q) = w;
+      if (!dupw) *reinterpret_cast<u32x4_t*>(yrow + b * 32 + 16 * q) = w;
     }
   };
   // Vector-memory issue order of iteration i:  residual loads of block i - 1 | DMA of chunk i + D | (MFMAs) | stores of the block
@@ -297,6 +303,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_xs_kernel(GemmParams p, int cp
 
   // accumulator sets are indexed statically (chunk c lives in set c % NACC): the loop is written NACC iterations at a time
   f32x16_t acc[NACC];
+  const int spb = dupw ? 0 : SPB;                      // stores this wave issues per output block
   auto iter = [&](int c, auto SLOT) {
     constexpr int S = decltype(SLOT)::value;
     // This wave's DMA of chunk c (issued in iteration c - D, after that iteration's residual loads) has landed when at most the
@@ -312,7 +319,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_xs_kernel(GemmParams p, int cp
       const int i = c - k;
       if (i < 0) continue;
       if (k != D) allow += (block_done_before(i) ? RPB : 0) + ((i + D < nch) ? DPC : 0);
-      allow += block_done_before(i) ? SPB : 0;
+      allow += block_done_before(i) ? spb : 0;
     }
     xs_vm_wait(allow);
     __builtin_amdgcn_s_barrier();                      // every wave's pieces landed; the slot of chunk c - 1 is free

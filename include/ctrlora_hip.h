@@ -111,7 +111,8 @@ typedef struct cl_gemm_params {
   int act;                            /* 0 none, 1 SiLU, 2 GEGLU (value / gate rows of W interleaved per 160-row tile, C is
                                          [M, N/2]: ldm/modules/attention.py:49-56 fused into the projection; no-grad forwards),
                                          3 (ABI 7) the same fusion with W's rows in their natural [value | gate] order:
-                                         bf16, K1 in {320, 640}, K2 in {0, 128}, N % 64 == 0 only -- CL_EINVAL otherwise,
+                                         bf16, K1 in {320, 640}, K2 in {0, 128}, N % 64 == 0 only -- CL_EINVAL otherwise
+                                         (the full list: "x-stationary-only forms" below),
                                          4 (added in ABI 7, compatible) exact GELU 0.5 x (1 + erf(x / sqrt 2)) of the fp32 sum
                                          A1.W1^T [+ A2.W2^T] + bias [+ rowbias], before alpha and beta * residual: CLIPMLP.fc1 +
                                          activation_fn (transformers/models/clip/modeling_clip.py:346-350, hidden_act "gelu") */
@@ -133,7 +134,8 @@ typedef struct cl_gemm_params {
    * exists in memory).  ln_gamma != NULL: A1 holds the UN-normalised rows and the kernel forms (row - mean) * rstd * gamma
    * + beta over the K1 columns before the contraction (fp32 statistics; rounded to `dtype` like cl_layernorm_fwd's output).
    * ln_stats (may be NULL): [M][2] fp32 {mean, rstd} for cl_layernorm_bwd.  bf16, linear mode, K1 in {320, 640}, K2 = 0,
-   * no rowbias / residual only -- CL_EINVAL otherwise (the caller then runs cl_layernorm_fwd itself). */
+   * no rowbias / residual only -- CL_EINVAL otherwise (the caller then runs cl_layernorm_fwd itself; the full list:
+   * "x-stationary-only forms" below). */
   const float* ln_gamma; const float* ln_beta; float ln_eps; float* ln_stats;
   /* Argument restrictions (CL_EINVAL otherwise; checked before any tile configuration is chosen, so they hold for every
    * configuration alike -- tests/test_gpu_gemm_conformance.py):
@@ -150,6 +152,21 @@ typedef struct cl_gemm_params {
    *   - a second K segment (K2 > 0) and grouped segments exist in CL_GEMM_LINEAR only;
    *   - alpha_n a multiple of 8 in [0, N]; a group width divides N, a2_group_n needs K2 > 0, and some tile width (64, 128
    *     or 160 columns) must divide every group width: a tile never straddles two groups.
+   * x-stationary-only forms: act 3 and the LayerNorm prologue (ln_gamma != NULL) have one kernel (csrc/gemm_xs.hip) and no
+   * fall-back, so what that kernel's launcher refuses is CL_EINVAL for the call (tests/test_gemm_xs_reference_model.py holds
+   * the table).  Both, beyond the restrictions above (the alpha_n and group ranges included):
+   *   - bf16 storage, CL_GEMM_LINEAR, no atomic, no out_f32, no rowbias, no a1_group_n;
+   *   - M >= 128 (a workgroup owns 128 rows; rows past M repeat row M - 1);
+   *   - K1 in {320, 640};
+   *   - lda1, ldw1, ldc (and lda2, ldw2 with K2, ldr with a residual) multiples of 8: every access is a 16-byte vector;
+   *   - alpha_n a multiple of 32 (alpha changes between 32-column output blocks);
+   *   - a2_group_n a multiple of 32 that divides N, with K2 > 0.
+   * act 3 only: N % 64 == 0 (C is [M, N / 2], whole 32-column blocks), K2 in {0, 128}, no residual, alpha == 1,
+   *   alpha_n == 0, a2_group_n == 0.
+   * LayerNorm prologue only: act 0 (N % 32 == 0) or act 3; ln_beta != NULL; K2 == 0; no residual.
+   * (Products WITH a fall-back never see these as refusals: where the x-stationary kernel is forced or tabled for a plain or
+   * residual product it does not take, the tile kernels run it.)  C == residual (in place) is part of the contract for every
+   * configuration: an element is read and written by its owner only.
    * rowbias and residual are read in `dtype` ([M / rows_per_batch, N] and [M, N]); with atomic, C is fp32 and the product is
    * added onto what it holds. */
 } cl_gemm_params;

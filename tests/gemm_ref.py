@@ -21,6 +21,17 @@ shows on the CPU that each of them bites):
   3. canary: the output is a view into a larger buffer (ldc = N + 8, 64 guard rows either side) pre-filled with a fixed
      non-NaN bit pattern, NaN inside the view; afterwards every guard row and pad column is bit-identical and no NaN is left;
   4. (GPU only) exactly one launch of the intended signature in the launch-tag table.
+
+The two forms only the x-stationary kernel has (csrc/gemm_xs.hip) widen the bound of check 2 by terms that
+are derived here, never measured:
+
+  * act = ACT_GEGLU_SPLIT (3): h = a1 w1^T [+ a2 w2^T] + bias, out[M, N / 2] = h[:, :N / 2] gelu_exact(h[:, N / 2:]).  The product
+    rule above, plus |value| |dgelu(gate)| for the kernel's Abramowitz-Stegun erfc (`dgelu_as`);
+  * ln = (gamma, beta, eps): xn = bf16_rne((x - mean) rstd gamma + beta) with fp64 statistics over the K1 stored values, then the
+    product on xn.  The kernel rounds xn from an fp32 value, so an element whose fp64 value lies within the fp32 error bound of
+    a bf16 tie (tests/norm_ref.py: fixed_y + C_STAT["ln"] stat_y) may round the other way: such elements are `ambiguous` and widen
+    the bound by |alpha| sum_k amb[m, k] ulp_bf16(xn[m, k]) |w[n, k]| (through the GEGLU product rule for act 3).  They are never
+    skipped.  `ln_parts` records the share of rows that carry a widening; tests/xs_ref.py draws inputs that keep it <= 2 %.
 """
 import math
 
@@ -32,7 +43,7 @@ TOL_ONE_ROUNDING = 2.5e-3
 TOL_F32 = 2e-5
 
 LINEAR, CONV_S1, CONV_S2, CONV_UP2, CONV_T2 = 0, 1, 2, 3, 4
-ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
+ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GEGLU_SPLIT = 0, 1, 2, 3
 LIP_SILU, LIP_GELU = 1.1, 1.1
 GUARD_ROWS, PAD_COLS = 64, 8
 # leading-dimension pads of the operands: all different from the output's, whole 128-byte lines in both dtypes
@@ -86,19 +97,20 @@ def _f32_gate(got, ref64, a, b):
 
 def make_case(a1, w1, *, a2=None, w2=None, bias=None, rowbias=None, rows_per_batch=0, residual=None, alpha=1.0, beta=0.0,
               act=ACT_NONE, mode=LINEAR, conv=None, a1_group_n=0, a2_group_n=0, alpha_n=0, out_f32=False, atomic=False,
-              splitk=1, c0=None, N=None):
+              splitk=1, c0=None, N=None, ln=None):
     """One cl_gemm call as plain data.  a1: [M, K1] (linear; [M, G K1] with a1_group_n) or NHWC pixels [B Hin Win, K1] (conv modes,
-    conv = (B, Hin, Win, Hout, Wout)); w1: [N, taps K1]; c0: the value C holds before an atomic launch."""
+    conv = (B, Hin, Win, Hout, Wout)); w1: [N, taps K1]; c0: the value C holds before an atomic launch; ln = (gamma [K1], beta [K1],
+    eps): a1 holds the un-normalised rows (LayerNorm prologue)."""
     c = dict(a1=a1, w1=w1, a2=a2, w2=w2, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch, residual=residual,
              alpha=float(alpha), beta=float(beta), act=act, mode=mode, conv=conv, a1_group_n=a1_group_n, a2_group_n=a2_group_n,
-             alpha_n=alpha_n, out_f32=bool(out_f32), atomic=bool(atomic), splitk=splitk, c0=c0)
+             alpha_n=alpha_n, out_f32=bool(out_f32), atomic=bool(atomic), splitk=splitk, c0=c0, ln=ln)
     c["N"] = w1.shape[0] if N is None else N
     taps = 1 if mode == LINEAR else 9
     c["K1"] = w1.shape[1] // taps
     c["K2"] = 0 if w2 is None else w2.shape[1]
     c["M"] = a1.shape[0] if mode == LINEAR else conv[0] * conv[3] * conv[4]
     c["dtype"] = a1.dtype
-    c["out_cols"] = c["N"] // 2 if act == ACT_GEGLU else c["N"]
+    c["out_cols"] = c["N"] // 2 if act in (ACT_GEGLU, ACT_GEGLU_SPLIT) else c["N"]
     c["out_dtype"] = torch.float32 if (out_f32 or atomic) else a1.dtype
     return c
 
@@ -106,7 +118,7 @@ def make_case(a1, w1, *, a2=None, w2=None, bias=None, rowbias=None, rows_per_bat
 def k_total(c):
     """Accumulated terms of one output element: the K of both segments plus one per rounding the epilogue adds."""
     epi = sum(1 for k in ("bias", "rowbias", "residual") if c[k] is not None) + (c["alpha"] != 1.0) + (c["beta"] not in (0.0, 1.0))
-    epi += {ACT_NONE: 0, ACT_SILU: 3, ACT_GEGLU: 6}[c["act"]]         # exp / erf, the sum and the quotient / products
+    epi += {ACT_NONE: 0, ACT_SILU: 3, ACT_GEGLU: 6, ACT_GEGLU_SPLIT: 6}[c["act"]]         # exp / erf, the sum and the quotient / products
     if c["atomic"]:
         epi += max(1, c["splitk"])                                  # one fp32 add onto C per split
     return (1 if c["mode"] == LINEAR else 9) * c["K1"] + c["K2"] + epi
@@ -146,6 +158,62 @@ def _conv64(c, a1, w, lo, hi, F):
     return y.permute(0, 2, 3, 1).reshape(hi - lo, N)
 
 
+def ulp_bf16(v):
+    """Spacing of the bf16 grid at |v| (fp64 tensor; 0 at v = 0): 2^(floor(log2 |v|) - 7)."""
+    _, e = torch.frexp(v)
+    return torch.where(v != 0, torch.ldexp(torch.ones_like(v), e - 8), torch.zeros_like(v))
+
+
+def ln_parts(c):
+    """The LayerNorm prologue of a case in fp64 (cached in the case): xn = bf16_rne(y) as double, amb_ulp = ulp_bf16(xn) where y
+    lies within its fp32 error bound of a bf16 tie and 0 elsewhere, mean / rstd with the parts of their gates (norm_ref),
+    amb_rows = the share of rows with an ambiguous element."""
+    if "_ln" not in c:
+        from tests import norm_ref as NR
+        gamma, beta, eps = c["ln"]
+        case = dict(family="ln", M=c["M"], D=c["K1"], silu=False, eps=eps, x=c["a1"], gamma=gamma, beta=beta)
+        r = NR.norm_ref64(case, backward=False, bounds=True)
+        y = r["y"]
+        xn = y.to(torch.bfloat16).double()
+        e32 = r["fixed_y"] + NR.C_STAT["ln"] * r["stat_y"]          # what a correct fp32 evaluation may be off by
+        u = ulp_bf16(y)
+        frac = (y.abs() / u.clamp_min(1e-300)) % 1.0
+        dist = (frac - 0.5).abs() * u                                # to the nearest midpoint of two bf16 neighbours
+        amb = (dist <= e32) & (y != 0)
+        c["_ln"] = dict(xn=xn, amb_ulp=torch.where(amb, ulp_bf16(xn), torch.zeros_like(xn)), mean=r["mean"], rstd=r["rstd"],
+                        stat_mean=r["stat_mean"], stat_rstd=r["stat_rstd"], amb_rows=float(amb.any(1).double().mean()),
+                        amb_elems=int(amb.sum()))
+    return c["_ln"]
+
+
+# gelu_as (csrc/gemm_xs.hip), to first order in e = 2^-24 from the code:
+#   z = |g| 0.7071..                       one rounding (the constant's own is below it): relative e
+#   t = rcp(fma(0.3275911, z, 1))          one rounding of the fma, the hardware reciprocal to 1 ulp = 2 e, and the error of z carried
+#                                          through (0.3275911 z t <= 1): relative 4 e in all
+#   P = ((((a5 t + a4) t + a3) t + a2) t + a1) t     four fma and one product: each rounds a partial sum that is at most
+#                                          S(t) = sum |a_i| t^i (the signs alternate), 5 e S(t); the error of t enters as
+#                                          |P'(t)| t 4 e <= 4 e S1(t), S1 = sum i |a_i| t^i
+#   E = exp2(-1.4427 z z)                  two products for the argument a = z^2 log2 e (2 e a), the error of z twice (2 e a) and
+#                                          the constant's rounding (e a / 2): |dE| / E = ln 2 . 4.5 e a = 4.5 e z^2; exp2 itself 1 ulp = 2 e
+#   c = P E  (one rounding)  ~ erfc(z)     A&S 7.1.26: |P E - erfc z| <= 1.5e-7 in exact arithmetic
+#   gelu = 0.5 g (c or 2 - c)              2 - c and the product: 2 e |gelu|
+_AS = (0.254829592, 0.284496736, 1.421413741, 1.453152027, 1.061405429)     # |a_1| .. |a_5|
+
+
+def dgelu_as(g):
+    """|gelu_as(g) - gelu(g)| at most, first order (fp64 tensor in, fp64 tensor out)."""
+    e = 2.0 ** -24
+    z = g.abs() * (0.5 ** 0.5)
+    t = 1.0 / (1.0 + 0.3275911 * z)
+    S = sum(a * t ** (i + 1) for i, a in enumerate(_AS))
+    S1 = sum((i + 1) * a * t ** (i + 1) for i, a in enumerate(_AS))
+    Ex = torch.exp(-z * z)
+    cc = torch.erfc(z)
+    dc = 1.5e-7 + e * ((5 * S + 4 * S1) * Ex + cc * (4.5 * z * z + 2 + 1))
+    gel = 0.5 * g * (1.0 + torch.erf(g * (0.5 ** 0.5)))
+    return 0.5 * g.abs() * dc + 2 * e * gel.abs()
+
+
 def _grouped(a, w, group_n, K):
     """Output columns [g group_n, (g + 1) group_n) read columns [g K, (g + 1) K) of a."""
     G = w.shape[0] // group_n
@@ -170,6 +238,8 @@ def gemm_ref64(c, lo=0, hi=None, absolute=False, kappa=0.0, dtype=torch.float64)
             s = _conv64(c, a1, w1, lo, hi, F)
         elif c["a1_group_n"]:
             s = _grouped(ab(cv(c["a1"][lo:hi])), w1, c["a1_group_n"], c["K1"])
+        elif c["ln"] is not None:
+            s = ab(ln_parts(c)["xn"][lo:hi].to(dtype)) @ w1.t()
         else:
             s = ab(cv(c["a1"][lo:hi])) @ w1.t()
         if c["a2"] is not None:
@@ -191,6 +261,11 @@ def gemm_ref64(c, lo=0, hi=None, absolute=False, kappa=0.0, dtype=torch.float64)
         val, gate = t[:, :, 0].reshape(hi - lo, -1), t[:, :, 1].reshape(hi - lo, -1)
         gel = 0.5 * gate * (1.0 + torch.erf(gate * (0.5 ** 0.5)))
         v = val * gel
+    elif c["act"] == ACT_GEGLU_SPLIT:
+        # natural row order, as nn.Linear(dim, 2 inner) holds them: [value | gate]
+        val, gate = s[:, :c["N"] // 2], s[:, c["N"] // 2:]
+        gel = 0.5 * gate * (1.0 + torch.erf(gate * (0.5 ** 0.5)))
+        v = val * gel
     else:
         v = s
     if absolute:
@@ -200,6 +275,9 @@ def gemm_ref64(c, lo=0, hi=None, absolute=False, kappa=0.0, dtype=torch.float64)
         elif c["act"] == ACT_GEGLU:
             t = m.reshape(hi - lo, c["N"] // 160, 2, 80)
             mv, mg = t[:, :, 0].reshape(hi - lo, -1), t[:, :, 1].reshape(hi - lo, -1)
+            v = gel.abs() * mv + LIP_GELU * mg * (val.abs() + kappa * mv)
+        elif c["act"] == ACT_GEGLU_SPLIT:
+            mv, mg = m[:, :c["N"] // 2], m[:, c["N"] // 2:]
             v = gel.abs() * mv + LIP_GELU * mg * (val.abs() + kappa * mv)
         else:
             v = m
@@ -214,6 +292,31 @@ def gemm_ref64(c, lo=0, hi=None, absolute=False, kappa=0.0, dtype=torch.float64)
     if c["atomic"] and c["c0"] is not None:
         v = v + (abs(c["c0"]) if absolute else c["c0"])
     return v
+
+
+def xs_extra(c, lo=0, hi=None):
+    """The additive part of the element-wise bound that the x-stationary-only forms need (module docstring), rows [lo, hi):
+    None for every other case."""
+    if c["ln"] is None and c["act"] != ACT_GEGLU_SPLIT:
+        return None
+    hi = c["M"] if hi is None else hi
+    half = c["N"] // 2
+    wid = None
+    if c["ln"] is not None:
+        wid = ln_parts(c)["amb_ulp"][lo:hi] @ c["w1"].double()[:c["N"]].abs().t()
+    if c["act"] == ACT_GEGLU_SPLIT:
+        s = gemm_ref64(dict(c, act=ACT_NONE, alpha=1.0, residual=None), lo, hi)          # h, before the activation
+        val, gate = s[:, :half], s[:, half:]
+        gel = 0.5 * gate * (1.0 + torch.erf(gate * (0.5 ** 0.5)))
+        ex = val.abs() * dgelu_as(gate)
+        if wid is not None:
+            wv, wg = wid[:, :half], wid[:, half:]
+            ex = ex + gel.abs() * wv + LIP_GELU * wg * (val.abs() + wv)
+        return ex
+    al = abs(c["alpha"])
+    if c["alpha"] != 1.0 and c["alpha_n"]:
+        return torch.cat([wid[:, :c["alpha_n"]] * al, wid[:, c["alpha_n"]:]], 1)
+    return wid * al
 
 
 # ------------------------------------------------------------------------------------------------ canary buffers
@@ -244,11 +347,12 @@ class Guarded:
         return dict(guard_rows=rows, pad_elems=pads, nan_left=int(torch.isnan(self.view).sum()))
 
 
-def padded(t, pad):
-    """A copy of the 2-D tensor t as a view with leading dimension t.shape[1] + pad; the pad holds PAD_FILL."""
+def padded(t, pad, fill=PAD_FILL):
+    """A copy of the 2-D tensor t as a view with leading dimension t.shape[1] + pad; the pad holds PAD_FILL (or `fill`: NaN for
+    a kernel that reads the operand through whole vectors inside its width only, so that no pad value may reach an output)."""
     if t is None:
         return None
-    buf = torch.full((t.shape[0], t.shape[1] + pad), PAD_FILL, dtype=t.dtype, device=t.device)
+    buf = torch.full((t.shape[0], t.shape[1] + pad), fill, dtype=t.dtype, device=t.device)
     buf[:, :t.shape[1]] = t
     return buf[:, :t.shape[1]]
 
@@ -272,6 +376,9 @@ def run_checks(c, got, guard=None, budget=1 << 25):
         se += float((err * err).nan_to_num(nan=0.0).sum())
         sr += float((ref * ref).sum())
         bound = u_out * ref.abs() + kappa * mag
+        extra = xs_extra(c, lo, hi)
+        if extra is not None:
+            bound = bound + extra
         bad = ~(err <= bound)                                  # a NaN in `got` is a violation
         ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, math.inf, 0.0)).nan_to_num(nan=math.inf)
         n = int(bad.sum())
@@ -284,6 +391,8 @@ def run_checks(c, got, guard=None, budget=1 << 25):
     rel = math.sqrt(se) / (math.sqrt(sr) + 1e-30)
     out = dict(rel=rel, gate=TOL_ONE_ROUNDING if bf16_out else TOL_F32, torch_f32=None, violations=viol, err_over_bound=worst,
                first_violation=first, k_total=kt)
+    if c["ln"] is not None:
+        out["amb_rows"] = ln_parts(c)["amb_rows"]
     if not bf16_out and not rel < out["gate"]:
         # the fp32 gate: twice what torch's own fp32 evaluation of the same expression loses, where that is larger
         s2 = sr2 = 0.0

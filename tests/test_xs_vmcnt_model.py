@@ -8,6 +8,8 @@ order, per wave, for every form that ships (ring depth 2 / 3; plain, residual, G
   * WAR: the DMA that refills a slot is issued after the barrier that follows the last reader of that slot;
   * the residual wait inside an iteration covers the residual loads and nothing newer than them but this iteration's DMA;
   * every block is stored exactly once, its residual loaded exactly once before it.
+A wave of the residual form whose 32 rows all lie past M (copies of row M - 1 only) issues NO stores -- in place it would race
+with the owner of the row -- and its count uses spb = 0: replayed as `dup`, with the same properties but for the stores.
 No GPU."""
 import pytest
 
@@ -30,10 +32,11 @@ def kernel_allow(c, nch, D, DPC, CPB, RPB, SPB):
     return allow
 
 
-def replay(nob, RING, KS, epi):
+def replay(nob, RING, KS, epi, dup=False):
     CPB = 2 if epi == "geglu" else 1
     RPB = 2 if epi == "res" else 0
-    SPB, D, DPC = 2, RING - 1, DPC_OF[KS]
+    assert not dup or epi == "res"                     # (the kernel: dupw = EPI == XS_RES && the wave's first row >= M)
+    SPB, D, DPC = (0 if dup else 2), RING - 1, DPC_OF[KS]
     nch = nob * CPB
     ops = []                       # issue order of one wave: (kind, index)
     dma_pos, res_pos, store_pos = {}, {}, {}
@@ -72,8 +75,20 @@ def replay(nob, RING, KS, epi):
                                           (3, 20, "res"), (2, 28, "res"), (3, 40, "res"),
                                           (3, 20, "geglu"), (2, 28, "geglu"), (3, 48, "geglu")])
 def test_counted_vmcnt_of_the_x_stationary_kernel(RING, KS, epi):
+    _check(RING, KS, epi, False)
+
+
+@pytest.mark.parametrize("RING,KS", [(3, 20), (2, 28), (3, 40), (3, 48)])
+def test_counted_vmcnt_of_a_copy_wave_of_the_residual_form(RING, KS):
+    """A wave that holds copies of row M - 1 only: no stores, spb = 0 in the count (and the K = 640 + 128 residual form, which the
+    list above leaves out, with its stores)."""
+    _check(RING, KS, "res", True)
+    _check(3, 48, "res", False)
+
+
+def _check(RING, KS, epi, dup):
     for nob in list(range(1, 14)) + [40, 80 if epi != "geglu" else 40]:
-        r = replay(nob, RING, KS, epi)
+        r = replay(nob, RING, KS, epi, dup)
         ops, nch, D = r["ops"], r["nch"], r["D"]
         for c, allow, issued in r["waits"]:
             # in-order retirement: after vmcnt(allow) the oldest (issued - allow) operations are complete
@@ -83,7 +98,7 @@ def test_counted_vmcnt_of_the_x_stationary_kernel(RING, KS, epi):
         for b, allow, issued in r["inner_waits"]:
             retired = issued - allow
             assert r["res_pos"][b] == retired - 1, (nob, b, "residual wait")
-            assert r["res_pos"][b] < r["store_pos"][b]
+            assert dup or r["res_pos"][b] < r["store_pos"][b]
         # WAR on the ring: chunk c + D goes into the slot chunk c - 1 was read from (iteration c - 1 ends before barrier c)
         first = {}
         for pos, (kind, idx) in enumerate(ops):
@@ -97,12 +112,22 @@ def test_counted_vmcnt_of_the_x_stationary_kernel(RING, KS, epi):
                 assert ch - D >= reader + 1                          # ... and that barrier is behind the reader's iteration
         # every block stored once, each residual loaded once and before its store
         stores = [i for k, i in ops if k == "store"]
-        assert sorted(set(stores)) == list(range(nob)) and len(stores) == 2 * nob
+        assert (stores == []) if dup else (sorted(set(stores)) == list(range(nob)) and len(stores) == 2 * nob)
         if epi == "res":
             loads = [i for k, i in ops if k == "res"]
             assert sorted(set(loads)) == list(range(nob)) and len(loads) == 2 * nob
         assert len([1 for k, _ in ops if k == "dma"]) == nch * DPC_OF[KS]
         assert max(a for _, a, _ in r["waits"]) <= 32                # the kernel's switch covers vmcnt(0) .. vmcnt(32)
+
+
+def test_a_copy_wave_counted_with_the_stores_it_does_not_issue_is_caught_by_the_model():
+    """The kernel's formula with SPB = 2 on a wave that issues no stores: the count is larger than what is in flight behind
+    DMA(c), so the wait can return before the chunk has landed."""
+    RING, KS = 3, 20
+    D, DPC = RING - 1, DPC_OF[KS]
+    r = replay(8, RING, KS, "res", dup=True)
+    bad = sum(1 for c, _, issued in r["waits"] if r["dma_pos"][c] >= issued - kernel_allow(c, r["nch"], D, DPC, 1, 2, 2))
+    assert bad > 0
 
 
 def test_a_wrong_count_is_caught_by_the_model():
