@@ -10,34 +10,12 @@ What changes underneath, not in the results:
   * schedule tables are computed exactly as the reference does (fp64 numpy / fp32 torch on the host) --
     index and timestep bookkeeping is bit-exact.
 """
-import contextlib
-
 import numpy as np
 import torch
 
+from ldm.models.diffusion.guided_loop import (COND_FIRST, UNCOND_FIRST, batch_conds, context_kv, engine_of, guided_eps,
+                                              hint_scope, run_steps)
 from ldm.modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
-
-
-def _cat_conds(c, u):
-    """Batch two conditioning dicts (or lists of dicts) along dim 0; None if their structure differs."""
-    if isinstance(c, dict) and isinstance(u, dict) and c.keys() == u.keys():
-        out = {}
-        for k in c:
-            a, b = c[k], u[k]
-            if isinstance(a, list) and isinstance(b, list) and len(a) == len(b) and all(
-                    torch.is_tensor(x) and torch.is_tensor(y) and x.shape == y.shape for x, y in zip(a, b)):
-                out[k] = [torch.cat([x, y], 0) for x, y in zip(a, b)]
-            elif a is None and b is None:
-                out[k] = None
-            elif isinstance(a, str) and a == b:
-                out[k] = a
-            else:
-                return None
-        return out
-    if isinstance(c, (list, tuple)) and isinstance(u, (list, tuple)) and len(c) == len(u):
-        parts = [_cat_conds(a, b) for a, b in zip(c, u)]
-        return None if any(p is None for p in parts) else parts
-    return None
 
 
 class DDIMSampler(object):
@@ -101,9 +79,7 @@ class DDIMSampler(object):
         size = (batch_size, C, H, W)
         if verbose:
             print(f"Data shape for DDIM sampling is {size}, eta {eta}")
-        # condition images do not change during a run: their VAE encode is done once (ControlLDM.hint_cache)
-        scope = getattr(self.model, "hint_cache", None) if self.hoist_hint_encode else None
-        with (scope() if callable(scope) else contextlib.nullcontext()):
+        with hint_scope(self.model, self.hoist_hint_encode):
             return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback,
                                       quantize_denoised=quantize_x0, mask=mask, x0=x0, ddim_use_original_steps=False,
                                       noise_dropout=noise_dropout, temperature=temperature,
@@ -134,12 +110,7 @@ class DDIMSampler(object):
                 and noise_dropout == 0. and callable(getattr(self.model, "engine", None))):
             return self._sampling_graphed(cond, img, timesteps, callback, img_callback, log_every_t, temperature,
                                           unconditional_guidance_scale, unconditional_conditioning, intermediates)
-        eng = getattr(self.model, "engine", None)
-        if callable(eng):
-            # text context is constant over the loop: project K/V of every cross-attention once
-            self.model.engine().cache_context_kv = True
-            self.model.engine().reset_context_cache()
-        try:
+        with context_kv(engine_of(self.model)):
             for i, step in enumerate(time_range):
                 index = total_steps - i - 1
                 ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -160,10 +131,6 @@ class DDIMSampler(object):
                 if index % log_every_t == 0 or index == total_steps - 1:
                     intermediates["x_inter"].append(img)
                     intermediates["pred_x0"].append(pred_x0)
-        finally:
-            if callable(eng):
-                self.model.engine().cache_context_kv = False
-                self.model.engine().reset_context_cache()
         return img, intermediates
 
     @torch.no_grad()
@@ -171,8 +138,8 @@ class DDIMSampler(object):
                           uncond, intermediates):
         """The S-step loop of ddim_sampling (:157-178) with the loop state on the DEVICE: a cursor i counts
         iterations, `cl_ddim_set_t` derives ts = ddim_timesteps[S-1-i] and `cl_ddim_step_dev` the table row, so
-        one step = both CFG passes through the engine + the fused update is a fixed kernel sequence.  Iteration 0
-        runs eagerly (fills the context K/V cache, sizes every buffer), iteration 1 is captured, the rest replay."""
+        one step = both CFG passes through the engine + the fused update is a fixed kernel sequence, which
+        guided_loop.run_steps captures once and replays (or, with a kept graph of the same problem, only replays)."""
         from ctrlora_amd import hip
         model, device = self.model, img.device
         S, b = int(timesteps.shape[0]), img.shape[0]
@@ -201,43 +168,42 @@ class DDIMSampler(object):
                bool(getattr(model, "only_mid_control", False)), bool(self.batch_cfg), bool(self.hoist_hint_encode), _plain(cond),
                _plain(uncond), WEIGHTS_GENERATION[0],
                tuple(a.ip_scale for a in model.engine().unet.ip_layers))
+
+        def after_step(i):     # x, pred_x0: the device state of the loop that runs (a kept graph's, or a fresh one)
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(pred_x0, i)
+            index = S - i - 1
+            if index % log_every_t == 0 or index == S - 1:
+                intermediates["x_inter"].append(x.clone())
+                intermediates["pred_x0"].append(pred_x0.clone())
+
         st = self._graph_state if self.reuse_graph else None
         # sample() rebuilds the coefficient table on every call: the kept graph reads ITS table by address (held in st), so a
         # hit needs equal contents, not the same tensor
         if (st is not None and st["key"] == key and not (callback or img_callback)
                 and st["coef"].shape == self.coef_table.shape and bool(torch.equal(st["coef"], self.coef_table))):
             # replay-only loop: same kernels, same buffers (the context K/V products of iteration 0 are still in st)
-            st["x"].copy_(img.float())
+            x, pred_x0 = st["x"], st["pred_x0"]
+            x.copy_(img.float())
             st["cursor"].zero_()
-            for i in range(S):
-                st["graph"].replay()
-                index = S - i - 1
-                if index % log_every_t == 0 or index == S - 1:
-                    intermediates["x_inter"].append(st["x"].clone())
-                    intermediates["pred_x0"].append(st["pred_x0"].clone())
+            run_steps(None, S, after_step, graph=st["graph"], keep_graph=True)
             self.graph_hits += 1
-            return st["x"].clone(), intermediates
+            return x.clone(), intermediates
         self._graph_state = None
         x = img.float().contiguous().clone()
         pred_x0 = torch.empty_like(x)
         ts = torch.zeros(b, dtype=torch.long, device=device)
         cursor = torch.zeros(1, dtype=torch.int32, device=device)
         table = torch.as_tensor(np.ascontiguousarray(timesteps).astype(np.int64)).to(device)
-        use_cfg = not (uncond is None or cfg_scale == 1.)
-        both = _cat_conds(cond, uncond) if (use_cfg and self.batch_cfg) else None
+        guide = None if cfg_scale == 1. else uncond      # None: no guidance, one pass
+        both = batch_conds(cond, guide, COND_FIRST, cat_tensors=False) if self.batch_cfg else None
         any_sigma = bool((self.coef_table[:, 2] != 0).any())
 
         def body():
             hip.ddim_set_t(table, cursor, S, ts)
-            e_u = None
-            if not use_cfg:
-                e_c = model.apply_model(x, ts, cond)
-            elif both is not None:
-                e = model.apply_model(torch.cat([x, x], 0), torch.cat([ts, ts], 0), both)
-                e_c, e_u = e[:b], e[b:]
-            else:
-                e_c = model.apply_model(x, ts, cond)
-                e_u = model.apply_model(x, ts, uncond)
+            e_c, e_u = guided_eps(model, x, ts, cond, guide, both, COND_FIRST)
             # the reference draws the sigma*noise term every step (:227); with eta = 0 every sigma is zero and
             # the draw cannot change the sample, so it is skipped (only the global RNG position differs)
             noise = noise_like(x.shape, device, False) * temperature if any_sigma else None
@@ -245,60 +211,25 @@ class DDIMSampler(object):
                               self.coef_table, cursor, S, float(cfg_scale), x, pred_x0)
             hip.tick(cursor)
 
-        eng = model.engine()
-        eng.cache_context_kv = True
-        eng.reset_context_cache()
-        graph = None
-        try:
-            for i in range(S):
-                index = S - i - 1
-                if i == 0:
-                    body()
-                elif i == 1:
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        body()
-                    graph.replay()      # capture does not execute
-                else:
-                    graph.replay()
-                if callback:
-                    callback(i)
-                if img_callback:
-                    img_callback(pred_x0, i)
-                if index % log_every_t == 0 or index == S - 1:
-                    intermediates["x_inter"].append(x.clone())
-                    intermediates["pred_x0"].append(pred_x0.clone())
-        finally:
-            eng.cache_context_kv = False
-            kv_keep = eng.detach_context_cache() if (self.reuse_graph and graph is not None) else None
-            eng.reset_context_cache()
-        out = x.clone()
-        if self.reuse_graph and graph is not None:
+        with context_kv(model.engine()) as eng:
+            graph = run_steps(body, S, after_step, keep_graph=self.reuse_graph)
+            kv_keep = eng.detach_context_cache() if graph is not None else None
+        if graph is not None:
             # the graph reads the cached K/V products and the conditioning tensors by address: hold them
             self._graph_state = dict(key=key, graph=graph, x=x, pred_x0=pred_x0, ts=ts, cursor=cursor, table=table, kv=kv_keep,
                                      conds=(cond, uncond, both), coef=self.coef_table,
                                      eng=eng)     # keeps id(engine) in `key` from being recycled by a rebuilt engine
-        del graph
-        return out, intermediates
+        return x.clone(), intermediates
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, dynamic_threshold=None):
         from ctrlora_amd import hip
-        b, device = x.shape[0], x.device
-        e_u = None
-        if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-            e_c = self.model.apply_model(x, t, c)
-        else:
-            both = _cat_conds(c, unconditional_conditioning) if self.batch_cfg else None
-            if both is not None:
-                e = self.model.apply_model(torch.cat([x, x], 0), torch.cat([t, t], 0), both)
-                e_c, e_u = e[:b].contiguous(), e[b:].contiguous()
-            else:
-                e_c = self.model.apply_model(x, t, c)
-                e_u = self.model.apply_model(x, t, unconditional_conditioning)
+        device = x.device
+        uc = None if unconditional_guidance_scale == 1. else unconditional_conditioning
+        both = batch_conds(c, uc, COND_FIRST, cat_tensors=False) if self.batch_cfg else None
+        e_c, e_u = guided_eps(self.model, x, t, c, uc, both, COND_FIRST)
         if self.model.parameterization != "eps":
             raise NotImplementedError("v-parameterisation is not used by the CtrLoRA configs")
         sigma_nonzero = float(self.coef_table[index, 2]) != 0.0 if noise_dropout > 0. else True
@@ -313,20 +244,6 @@ class DDIMSampler(object):
         return x_prev, pred_x0
 
     # ------------------------------------------------------------------ inversion / img2img helpers
-    def _eps_pair(self, x, t, c, scale, uc):
-        """(eps_cond, eps_uncond or None) for one inversion step.  With guidance the reference evaluates ONE batch of 2B
-        ordered [unconditional; conditional] (cldm/ddim_hacked.py:257-262); tensors and same-structure dict conditionings
-        are batched that way here, anything else runs as two passes (the samples are independent)."""
-        if scale == 1.:
-            return self.model.apply_model(x, t, c), None
-        assert uc is not None
-        b = x.shape[0]
-        both = torch.cat((uc, c)) if torch.is_tensor(c) and torch.is_tensor(uc) else _cat_conds(uc, c)
-        if both is not None:
-            e = self.model.apply_model(torch.cat((x, x)), torch.cat((t, t)), both)
-            return e[b:].contiguous(), e[:b].contiguous()
-        return self.model.apply_model(x, t, c), self.model.apply_model(x, t, uc)
-
     @torch.no_grad()
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None):
@@ -353,9 +270,15 @@ class DDIMSampler(object):
         b = x.shape[0]
         kept, kept_at = [], []
         every = (n // return_intermediates) if return_intermediates else 0
+        # With guidance the reference evaluates ONE batch of 2B ordered [unconditional; conditional] (cldm/ddim_hacked.py:
+        # 257-262); tensors and same-structure dict conditionings are batched that way here, anything else runs as two passes
+        # (the samples are independent)
+        uc = None if unconditional_guidance_scale == 1. else unconditional_conditioning
+        assert uc is not None or unconditional_guidance_scale == 1.
+        both = batch_conds(c, uc, UNCOND_FIRST, cat_tensors=True)
         for i in range(n):
             t = torch.full((b,), int(steps_all[i]), device=self.model.device, dtype=torch.long)
-            e_c, e_u = self._eps_pair(x, t, c, unconditional_guidance_scale, unconditional_conditioning)
+            e_c, e_u = guided_eps(self.model, x, t, c, uc, both, UNCOND_FIRST)
             x_new = torch.empty_like(x)
             hip.ddim_step(x, e_c.float().contiguous(), None if e_u is None else e_u.float().contiguous(), None, table, i,
                           float(unconditional_guidance_scale), x_new, None)

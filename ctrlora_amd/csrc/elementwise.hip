@@ -361,11 +361,13 @@ __global__ __launch_bounds__(64) void plosses_finish_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- DDIM update (ddim_hacked.py:192,203-231)
-// coef = device table [S][4] = {a_t, a_prev, sigma_t, sqrt(1 - a_t)} (fp32), row `index` is used.
-__global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ e_c,
-                                 const float* __restrict__ e_u, const float* __restrict__ noise,
-                                 const float* __restrict__ coef, int index, float scale,
-                                 float* __restrict__ x_prev, float* __restrict__ pred_x0, long n) {
+// coef = device table [S][4] = {a_t, a_prev, sigma_t, sqrt(1 - a_t)} (fp32), row `index` is used.  x_prev may alias x
+// (element-wise), so neither is __restrict__.  One body for the host-index and the device-cursor launch (below): an eager
+// and a replayed step give the same bits.
+__device__ __forceinline__ void ddim_step_body(const float* x, const float* __restrict__ e_c,
+                                               const float* __restrict__ e_u, const float* __restrict__ noise,
+                                               const float* __restrict__ coef, int index, float scale, float* x_prev,
+                                               float* __restrict__ pred_x0, long n) {
   const float a_t = coef[index * 4 + 0], a_prev = coef[index * 4 + 1];
   const float sigma = coef[index * 4 + 2], s1m = coef[index * 4 + 3];
   const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.0f - a_prev - sigma * sigma);
@@ -378,6 +380,11 @@ __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __res
     x_prev[i] = xp;
     if (pred_x0) pred_x0[i] = p0;
   }
+}
+__global__ void ddim_step_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                 const float* __restrict__ noise, const float* __restrict__ coef, int index, float scale,
+                                 float* x_prev, float* __restrict__ pred_x0, long n) {
+  ddim_step_body(x, e_c, e_u, noise, coef, index, scale, x_prev, pred_x0, n);
 }
 
 // ---------------------------------------------------------------- fused AdamW over one flat fp32 buffer
@@ -425,23 +432,11 @@ __global__ void ddim_set_t_kernel(const long* __restrict__ table, const int* __r
   const int index = max(0, S - 1 - *cursor);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) ts[i] = table[index];
 }
-__global__ void ddim_step_dev_kernel(const float* __restrict__ x, const float* __restrict__ e_c,
-                                     const float* __restrict__ e_u, const float* __restrict__ noise,
-                                     const float* __restrict__ coef, const int* __restrict__ cursor, int S,
-                                     float scale, float* __restrict__ x_prev, float* __restrict__ pred_x0, long n) {
-  const int index = max(0, S - 1 - *cursor);
-  const float a_t = coef[index * 4 + 0], a_prev = coef[index * 4 + 1];
-  const float sigma = coef[index * 4 + 2], s1m = coef[index * 4 + 3];
-  const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.0f - a_prev - sigma * sigma);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float e = e_c[i];
-    if (e_u) { const float u = e_u[i]; e = u + scale * (e - u); }
-    const float p0 = (x[i] - s1m * e) / sqrt_at;
-    float xp = sqrt_ap * p0 + dir * e;
-    if (noise) xp += sigma * noise[i];
-    x_prev[i] = xp;            // x_prev may alias x (element-wise)
-    if (pred_x0) pred_x0[i] = p0;
-  }
+__global__ void ddim_step_dev_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                     const float* __restrict__ noise, const float* __restrict__ coef,
+                                     const int* __restrict__ cursor, int S, float scale, float* x_prev,
+                                     float* __restrict__ pred_x0, long n) {
+  ddim_step_body(x, e_c, e_u, noise, coef, max(0, S - 1 - *cursor), scale, x_prev, pred_x0, n);
 }
 
 // ---------------------------------------------------------------- DPM-Solver++ multistep update (data prediction)

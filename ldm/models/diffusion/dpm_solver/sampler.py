@@ -16,12 +16,10 @@ What changes underneath, not in the results:
     (cl_dpm_set_t, apply_model, cl_dpmpp_step_dev, cl_tick) is captured as a hipGraph and replayed.
 Tensors outside the engine (CPU) take the same table through a plain-torch update.
 """
-import contextlib
-
 import numpy as np
 import torch
 
-from cldm.ddim_hacked import _cat_conds
+from ldm.models.diffusion.guided_loop import UNCOND_FIRST, batch_conds, context_kv, engine_of, guided_eps, hint_scope, run_steps
 
 
 def dpmpp_table(alphas_cumprod, S, order=2, skip_type="time_uniform"):
@@ -120,42 +118,28 @@ class DPMSolverSampler(object):
             print(f"Data shape for DPM-Solver sampling is {size}, sampling steps {S}")
         device = self.model.betas.device
         img = torch.randn(size, device=device) if x_T is None else x_T.to(device)
-        cond, uncond, scale = conditioning, unconditional_conditioning, float(unconditional_guidance_scale)
-        use_cfg = not (uncond is None or scale == 1.)
-        both = None
-        if use_cfg and self.batch_cfg:
-            both = torch.cat([uncond, cond]) if torch.is_tensor(cond) and torch.is_tensor(uncond) else _cat_conds(uncond, cond)
-        scope = getattr(self.model, "hint_cache", None) if self.hoist_hint_encode else None
-        with (scope() if callable(scope) else contextlib.nullcontext()):
+        cond, scale = conditioning, float(unconditional_guidance_scale)
+        uncond = None if scale == 1. else unconditional_conditioning       # None: no guidance, one pass
+        both = batch_conds(cond, uncond, UNCOND_FIRST, cat_tensors=True) if self.batch_cfg else None
+        with hint_scope(self.model, self.hoist_hint_encode):
             if not img.is_cuda:
-                x = self._loop_torch(img, cond, uncond, both, use_cfg, scale)
-            elif self.use_graph and int(S) >= 4 and callable(getattr(self.model, "engine", None)):
-                x = self._loop_graphed(img, cond, uncond, both, use_cfg, scale)
+                x = self._loop_torch(img, cond, uncond, both, scale)
+            elif self.use_graph and int(S) >= 4 and engine_of(self.model) is not None:
+                x = self._loop_graphed(img, cond, uncond, both, scale)
             else:
-                x = self._loop_eager(img, cond, uncond, both, use_cfg, scale)
+                x = self._loop_eager(img, cond, uncond, both, scale)
         return x, None
 
-    # ------------------------------------------------------------------ one model evaluation
-    def _eps_pair(self, x, ts, cond, uncond, both, use_cfg):
-        """(eps_cond, eps_uncond or None); ts has 2B entries when the two passes run as one batch [uncond; cond]."""
-        if not use_cfg:
-            return self.model.apply_model(x, ts, cond), None
-        if both is not None:
-            b = x.shape[0]
-            e = self.model.apply_model(torch.cat([x, x]), ts, both)
-            return e[b:], e[:b]
-        return self.model.apply_model(x, ts, cond), self.model.apply_model(x, ts, uncond)
-
     # ------------------------------------------------------------------ tensors outside the engine
-    def _loop_torch(self, img, cond, uncond, both, use_cfg, scale):
+    def _loop_torch(self, img, cond, uncond, both, scale):
         x = img.float()
         S, tab = self.coef_table.shape[0], self.coef_table
         nb = x.shape[0] * (2 if both is not None else 1)
         hist = [None, None, None]
         for i in range(S):
             alpha, sigma, cx, c0, c1, c2, t_in = (tab[i, k] for k in range(7))
-            e_c, e_u = self._eps_pair(x, torch.full((nb,), float(t_in), dtype=torch.float32, device=x.device), cond, uncond,
-                                      both, use_cfg)
+            ts = torch.full((nb,), float(t_in), dtype=torch.float32, device=x.device)
+            e_c, e_u = guided_eps(self.model, x, ts, cond, uncond, both, UNCOND_FIRST)
             e = e_c.float() if e_u is None else e_u.float() + scale * (e_c.float() - e_u.float())
             m = (x - sigma * e) / alpha
             hist[i % 3] = m
@@ -167,42 +151,28 @@ class DPMSolverSampler(object):
         return x
 
     # ------------------------------------------------------------------ GPU, every step eager
-    @contextlib.contextmanager
-    def _context_kv(self):
-        """The text context is constant over the loop: project K/V of every cross-attention once (engine models)."""
-        eng = self.model.engine() if callable(getattr(self.model, "engine", None)) else None
-        if eng is not None:
-            eng.cache_context_kv = True
-            eng.reset_context_cache()
-        try:
-            yield
-        finally:
-            if eng is not None:
-                eng.cache_context_kv = False
-                eng.reset_context_cache()
-
     def _state(self, img, both):
         x = img.float().contiguous().clone()
         nb = x.shape[0] * (2 if both is not None else 1)
         hist = torch.empty((3, x.numel()), dtype=torch.float32, device=x.device)
         return x, torch.empty_like(x), hist, nb, self.coef_table.to(x.device)
 
-    def _loop_eager(self, img, cond, uncond, both, use_cfg, scale):
+    def _loop_eager(self, img, cond, uncond, both, scale):
         from ctrlora_amd import hip
         x, pred_x0, hist, nb, coef = self._state(img, both)
-        with self._context_kv():
+        with context_kv(engine_of(self.model)):
             for i in range(coef.shape[0]):
                 ts = torch.full((nb,), float(self.coef_table[i, 6]), dtype=torch.float32, device=x.device)
-                e_c, e_u = self._eps_pair(x, ts, cond, uncond, both, use_cfg)
+                e_c, e_u = guided_eps(self.model, x, ts, cond, uncond, both, UNCOND_FIRST)
                 hip.dpmpp_step(x, e_c.float().contiguous(), None if e_u is None else e_u.float().contiguous(), coef, i, scale,
                                hist, x, pred_x0)
         return x
 
     # ------------------------------------------------------------------ GPU, one captured step replayed
-    def _loop_graphed(self, img, cond, uncond, both, use_cfg, scale):
+    def _loop_graphed(self, img, cond, uncond, both, scale):
         """Loop state on the device, as DDIMSampler._sampling_graphed: a cursor i counts iterations, cl_dpm_set_t writes the
-        model time of row i, cl_dpmpp_step_dev reads row i and the history slots i % 3, (i + 2) % 3, (i + 1) % 3.  Iteration 0
-        runs eagerly (fills the context K/V cache, sizes every buffer), iteration 1 is captured, the rest replay."""
+        model time of row i, cl_dpmpp_step_dev reads row i and the history slots i % 3, (i + 2) % 3, (i + 1) % 3.  One step is
+        then a fixed kernel sequence: guided_loop.run_steps captures it once and replays it."""
         from ctrlora_amd import hip
         x, pred_x0, hist, nb, coef = self._state(img, both)
         S = coef.shape[0]
@@ -211,25 +181,11 @@ class DPMSolverSampler(object):
 
         def body():
             hip.dpm_set_t(coef, cursor, S, ts)
-            e_c, e_u = self._eps_pair(x, ts, cond, uncond, both, use_cfg)
+            e_c, e_u = guided_eps(self.model, x, ts, cond, uncond, both, UNCOND_FIRST)
             hip.dpmpp_step_dev(x, e_c.float().contiguous(), None if e_u is None else e_u.float().contiguous(), coef, cursor, S,
                                scale, hist, x, pred_x0)
             hip.tick(cursor)
 
-        graph = None
-        with self._context_kv():
-            for i in range(S):
-                if i == 0:
-                    body()
-                elif i == 1:
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        body()
-                    graph.replay()      # capture does not execute
-                else:
-                    graph.replay()
-            out = x.clone()
-            torch.cuda.synchronize()    # the graph's buffers must outlive its last replay
-        del graph
-        return out
+        with context_kv(engine_of(self.model)):
+            run_steps(body, S)      # keeps no graph: it has waited for the last replay when it returns
+            return x.clone()

@@ -126,6 +126,7 @@ def test_inference_executor_rank512_latent32_eps_vs_oracle():
     form and gates as test_inference_executor_sd15_latent64_eps_vs_oracle."""
     _need_gpu()
     import bench
+    from ldm.models.diffusion.guided_loop import context_kv
     from oracle import arch
     from tests.test_gpu_parity_r3 import _oracle_eps
     from dataclasses import replace
@@ -147,14 +148,9 @@ def test_inference_executor_rank512_latent32_eps_vs_oracle():
     eps = model.apply_model(x, t, cond)
     ref = _oracle_eps(cfg, sd_cn, sd_un, x, t, ctx, hint)
     e = rel_l2(eps, ref)
-    eng.cache_context_kv = True
-    eng.reset_context_cache()
-    try:
+    with context_kv(eng):
         model.apply_model(x, t, cond)
         eps_kv = model.apply_model(x, t, cond)
-    finally:
-        eng.cache_context_kv = False
-        eng.reset_context_cache()
     e_kv = rel_l2(eps_kv, ref)
     cmp_ = rel_l2(_oracle_eps(cfg, sd_cn, sd_un, x, t, ctx, hint, autocast=True), ref)
     _record("inference_rank512_eps_vs_oracle", B=B, H=H, eps=e, eps_kv_cached=e_kv, comparator_bf16_autocast=cmp_)

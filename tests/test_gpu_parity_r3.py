@@ -49,6 +49,7 @@ def test_inference_executor_sd15_latent64_eps_vs_oracle():
     """configs[4]: eps of the inference executor (folded LoRA) at B = 4 and B = 16, with and without the context K/V
     cache, vs the fp32 oracle; the bf16-autocast oracle is measured beside it."""
     _need_gpu()
+    from ldm.models.diffusion.guided_loop import context_kv
     from oracle import arch
     cfg = arch.SD15
     model, sd_cn, sd_un = _inference_model()
@@ -64,14 +65,9 @@ def test_inference_executor_sd15_latent64_eps_vs_oracle():
         ref = _oracle_eps(cfg, sd_cn, sd_un, x, t, ctx, hint)
         e = rel_l2(eps, ref)
         # the same call through the context-K/V cache (first call fills it, the second one reads it)
-        eng.cache_context_kv = True
-        eng.reset_context_cache()
-        try:
+        with context_kv(eng):
             model.apply_model(x, t, cond)
             eps_kv = model.apply_model(x, t, cond)
-        finally:
-            eng.cache_context_kv = False
-            eng.reset_context_cache()
         e_kv = rel_l2(eps_kv, ref)
         cmp_ = rel_l2(_oracle_eps(cfg, sd_cn, sd_un, x, t, ctx, hint, autocast=True), ref)     # measured at both batch sizes (round 6)
         _record("inference_eps_vs_oracle", B=B, eps=e, eps_kv_cached=e_kv, comparator_bf16_autocast=cmp_)

@@ -83,8 +83,8 @@ def test_style_graphed_ddim_matches_eager_and_recaptures():
         return s.sample(S, B, (4, H, H), c, verbose=False, eta=0.0, x_T=x_T, unconditional_guidance_scale=7.5,
                         unconditional_conditioning=u)[0]
 
-    from cldm.ddim_hacked import _cat_conds
-    both = _cat_conds(cond, unc)
+    from ldm.models.diffusion.guided_loop import cat_conds
+    both = cat_conds(cond, unc)
     assert both is not None and both["c_ip"][0].shape[0] == 2 * B      # c_ip rides the 2B CFG batch
     eager = DDIMSampler(model)
     eager.use_graph = False

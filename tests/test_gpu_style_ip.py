@@ -117,6 +117,7 @@ def _tiny_ip_state(cfg, seed, scales):
 def test_engine_ip_scale_zero_and_no_context_are_the_plain_unet():
     _need_gpu()
     from ctrlora_amd.engine import CtrLoRAEngine, NetCfg
+    from ldm.models.diffusion.guided_loop import context_kv
     from oracle import arch
     cfg = arch.TINY
     ncfg = NetCfg(cfg.in_channels, cfg.out_channels, cfg.model_channels, cfg.channel_mult, cfg.num_res_blocks,
@@ -142,12 +143,9 @@ def test_engine_ip_scale_zero_and_no_context_are_the_plain_unet():
         e_ip = mixed.forward(z, t, ctx, [hint], context_ip=cip)
         assert rel_l2(e_ip, e_plain) > 1e-3          # the image prompt reaches eps
         # the per-key cache of a sampling run gives the same eps as the uncached pass
-        mixed.cache_context_kv = True
-        mixed.reset_context_cache()
-        assert torch.equal(mixed.forward(z, t, ctx, [hint], context_ip=cip), e_ip)
-        assert torch.equal(mixed.forward(z, t, ctx, [hint], context_ip=cip), e_ip)
-        mixed.cache_context_kv = False
-        mixed.reset_context_cache()
+        with context_kv(mixed):
+            assert torch.equal(mixed.forward(z, t, ctx, [hint], context_ip=cip), e_ip)
+            assert torch.equal(mixed.forward(z, t, ctx, [hint], context_ip=cip), e_ip)
         if dtype == torch.float32:
             e32 = e_ip
         else:
