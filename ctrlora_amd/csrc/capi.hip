@@ -358,5 +358,7 @@ int cl_timestep_embedding_f(int dtype, const float* t, const float* freqs, void*
 int cl_dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* coef, int index, int S_, float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream) { return dpmpp_step(x, e_c, e_u, coef, index, S_, scale, hist, x_next, pred_x0, n, S(stream)); }
 int cl_dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S_, float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream) { return dpmpp_step_dev(x, e_c, e_u, coef, cursor, S_, scale, hist, x_next, pred_x0, n, S(stream)); }
 int cl_dpm_set_t(const float* coef, const int* cursor, int S_, float* ts, int n, void* stream) { return dpm_set_t(coef, cursor, S_, ts, n, S(stream)); }
+int cl_plms_step(const float* x, const float* e_c, const float* e_u, const float* coef, int iter, int S_, int phase, float scale, float* hist, float* x_out, float* pred_x0, long n, void* stream) { return plms_step(x, e_c, e_u, coef, iter, S_, phase, scale, hist, x_out, pred_x0, n, S(stream)); }
+int cl_plms_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S_, float scale, float* hist, float* x_out, float* pred_x0, long n, void* stream) { return plms_step_dev(x, e_c, e_u, coef, cursor, S_, scale, hist, x_out, pred_x0, n, S(stream)); }
 
 }  // extern "C"

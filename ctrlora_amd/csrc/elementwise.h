@@ -8,13 +8,13 @@ namespace cl {
 // Every launcher resets it on entry and ew_done() (elementwise.hip) writes it after the launch check, so a refused or failed
 // call leaves id = 0.  form / aux: colsum 1 = block partials + finishing kernel, 2 = atomics, aux = pixel chunks; zero: bit 0 =
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
-// transpose: form = the input's dtype; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2).
+// transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2).
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
   EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
-  EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR
+  EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV
 };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
@@ -62,6 +62,12 @@ int dpmpp_step(const float* x, const float* e_c, const float* e_u, const float* 
 int dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
                    float scale, float* hist, float* x_next, float* pred_x0, long n, hipStream_t st);
 int dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, hipStream_t st);
+// PLMS update over DDIM's [S][4] table and a [4][n] ring of guided eps; phase 0 multistep, 1 start, 2 finish the start
+// (elementwise.hip; EwLaunchRec.form = phase)
+int plms_step(const float* x, const float* e_c, const float* e_u, const float* coef, int iter, int S, int phase, float scale,
+              float* hist, float* x_out, float* pred_x0, long n, hipStream_t st);
+int plms_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                  float scale, float* hist, float* x_out, float* pred_x0, long n, hipStream_t st);
 int adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
           float wd, int step, float gscale, hipStream_t st);
 int pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, hipStream_t st);

@@ -488,6 +488,58 @@ __global__ void dpm_set_t_kernel(const float* __restrict__ coef, const int* __re
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) ts[i] = t;
 }
 
+// ---------------------------------------------------------------- PLMS update (pseudo linear multistep, arXiv:2202.09778)
+// coef = DDIM's device table [S][4] fp32 {a_t, a_prev, sigma_t, sqrt(1 - a_t)}; iteration `iter` uses row S - 1 - iter.
+// hist = [4][n] fp32 ring, the guided eps of iteration k lives in slot k % 4.  upd(x, e') is DDIM's update:
+//   pred_x0 = (x - sqrt(1 - a_t) e') / sqrt(a_t),   x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma_t^2) e'
+// phase PLMS_MULTISTEP (iter >= 1): e = guided eps, hist[iter % 4] = e, e' = Adams-Bashforth over e and the last
+//   min(iter, 3) slots ((3 e - o1) / 2, (23 e - 16 o1 + 5 o2) / 12, (55 e - 59 o1 + 37 o2 - 9 o3) / 24), upd(x, e').
+// phase PLMS_START (iter 0): hist[0] = e, x_out = upd(x, e).x_prev (the predictor; pred_x0 is not written).
+// phase PLMS_FINISH (iter 0): e_n = guided eps at the predictor, e' = (hist[0] + e_n) / 2, upd(x, e'); hist is not written.
+// A slot that is not part of the order is not read (it is uninitialised in the first iterations).  x_out may alias x
+// (element-wise), so neither is __restrict__.  One body for the host-index and the device-cursor launch: an eager and a
+// replayed step give the same bits.
+enum { PLMS_MULTISTEP = 0, PLMS_START = 1, PLMS_FINISH = 2 };
+__device__ __forceinline__ void plms_step_body(const float* x, const float* __restrict__ e_c,
+                                               const float* __restrict__ e_u, const float* __restrict__ coef, int iter,
+                                               int S, int phase, float scale, float* hist, float* x_out,
+                                               float* __restrict__ pred_x0, long n) {
+  const float* row = coef + (long)(S - 1 - iter) * 4;
+  const float a_t = row[0], a_prev = row[1], sigma = row[2], s1m = row[3];
+  const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir = sqrtf(1.0f - a_prev - sigma * sigma);
+  const int order = phase == PLMS_MULTISTEP ? min(iter, 3) : 0;      // how many older slots enter e'
+  float* hw = hist + (long)(iter % 4) * n;
+  const float* o1 = hist + (long)((iter + 3) % 4) * n;
+  const float* o2 = hist + (long)((iter + 2) % 4) * n;
+  const float* o3 = hist + (long)((iter + 1) % 4) * n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float e = e_c[i];
+    if (e_u) { const float u = e_u[i]; e = u + scale * (e - u); }
+    float ep = e;
+    if (phase == PLMS_FINISH) ep = (hw[i] + e) / 2.0f;
+    else if (order == 1) ep = (3.0f * e - o1[i]) / 2.0f;
+    else if (order == 2) ep = (23.0f * e - 16.0f * o1[i] + 5.0f * o2[i]) / 12.0f;
+    else if (order == 3) ep = (55.0f * e - 59.0f * o1[i] + 37.0f * o2[i] - 9.0f * o3[i]) / 24.0f;
+    if (phase != PLMS_FINISH) hw[i] = e;
+    const float p0 = (x[i] - s1m * ep) / sqrt_at;
+    x_out[i] = sqrt_ap * p0 + dir * ep;
+    if (pred_x0 && phase != PLMS_START) pred_x0[i] = p0;
+  }
+}
+__global__ void plms_step_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                 const float* __restrict__ coef, int iter, int S, int phase, float scale, float* hist,
+                                 float* x_out, float* __restrict__ pred_x0, long n) {
+  plms_step_body(x, e_c, e_u, coef, iter, S, phase, scale, hist, x_out, pred_x0, n);
+}
+// device cursor = the iteration number, clamped to the multistep range [1, S - 1] (the start iteration never replays,
+// and a replay past the end cannot index outside the table)
+__global__ void plms_step_dev_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                     const float* __restrict__ coef, const int* __restrict__ cursor, int S, float scale,
+                                     float* hist, float* x_out, float* __restrict__ pred_x0, long n) {
+  const int iter = min(max(*cursor, 1), S - 1);
+  plms_step_body(x, e_c, e_u, coef, iter, S, PLMS_MULTISTEP, scale, hist, x_out, pred_x0, n);
+}
+
 // ---------------------------------------------------------------- 2x2 sum pool (data-gradient of nearest x2)
 // in [B, 2H, 2W, C] (ldi) -> out [B, H, W, C] (ldo), out (+)= sum of the 2x2 block
 template <typename T>
@@ -1015,6 +1067,28 @@ int dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, hip
   if (S < 1 || n < 1 || !coef || !cursor || !ts) return CL_EINVAL;
   hipLaunchKernelGGL(dpm_set_t_kernel, dim3(1), dim3(256), 0, st, coef, cursor, S, ts, n);
   return ew_done(EW_DPM_SET_T, -1, dim3(1), 256);
+}
+int plms_step(const float* x, const float* e_c, const float* e_u, const float* coef, int iter, int S, int phase, float scale,
+              float* hist, float* x_out, float* pred_x0, long n, hipStream_t st) {
+  ew_rec_begin();
+  if (S < 1 || iter < 0 || iter >= S || n < 0) return CL_EINVAL;
+  if (phase < PLMS_MULTISTEP || phase > PLMS_FINISH || (phase == PLMS_MULTISTEP) == (iter == 0)) return CL_EINVAL;
+  if (!x || !e_c || !coef || !hist || !x_out) return CL_EINVAL;
+  if (phase == PLMS_START && x_out == x) return CL_EINVAL;      // PLMS_FINISH updates the iteration's ORIGINAL input
+  if (n == 0) return CL_OK;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(plms_step_kernel, grid, dim3(256), 0, st, x, e_c, e_u, coef, iter, S, phase, scale, hist, x_out, pred_x0, n);
+  return ew_done(EW_PLMS_STEP, -1, grid, 256, phase);
+}
+int plms_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                  float scale, float* hist, float* x_out, float* pred_x0, long n, hipStream_t st) {
+  ew_rec_begin();
+  if (S < 2 || n < 0) return CL_EINVAL;
+  if (!x || !e_c || !coef || !cursor || !hist || !x_out) return CL_EINVAL;
+  if (n == 0) return CL_OK;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(plms_step_dev_kernel, grid, dim3(256), 0, st, x, e_c, e_u, coef, cursor, S, scale, hist, x_out, pred_x0, n);
+  return ew_done(EW_PLMS_STEP_DEV, -1, grid, 256);
 }
 int pool2x2(int dtype, const void* in, long ldi, void* out, long ldo, int B, int H, int W, int C, int accumulate, hipStream_t st) {
   ew_rec_begin();

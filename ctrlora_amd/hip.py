@@ -123,6 +123,8 @@ _SIGS = {
     "cl_dpmpp_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
     "cl_dpm_set_t": [_P, _P, _I, _P, _I, _P],
     "cl_posterior_sample_pair": [_P, _P, _P, _P, _P, _P, _I, _L, _F, _P],
+    "cl_plms_step": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _L, _P],
+    "cl_plms_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
 }
 EXPORTED = tuple(_SIGS.keys())
 # probe hooks (ctrlora_amd/csrc/debug_hooks.h): exported by the library, not part of include/ctrlora_hip.h
@@ -827,3 +829,36 @@ def dpm_set_t(coef, cursor, S, ts):
     assert ts.dtype == torch.float32 and ts.is_contiguous() and tuple(coef.shape) == (S, 8)
     _chk(lib().cl_dpm_set_t(coef.data_ptr(), cursor.data_ptr(), S, ts.data_ptr(), ts.numel(), stream()), "cl_dpm_set_t")
     return ts
+
+
+# phases of cl_plms_step: the multistep update of iterations >= 1; iteration 0's predictor; iteration 0's final update
+PLMS_MULTISTEP, PLMS_START, PLMS_FINISH = 0, 1, 2
+
+
+def _plms_args(x, e_c, e_u, coef, S, hist, x_out, pred_x0):
+    n = x.numel()
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (S, 4), tuple(coef.shape)
+    assert hist.dtype == torch.float32 and hist.is_contiguous() and hist.numel() == 4 * n
+    for t in (x, e_c, e_u, x_out, pred_x0):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    return n
+
+
+def plms_step(x, e_c, e_u, coef, iteration, phase, scale, hist, x_out, pred_x0=None):
+    """One PLMS update of iteration `iteration` on DDIM's [S][4] table (row S - 1 - iteration) and the [4][n] eps ring
+    (cl_plms_step).  phase: PLMS_MULTISTEP (iteration >= 1), PLMS_START / PLMS_FINISH (iteration 0: the predictor into an
+    x_out that is not x, then the final update of the ORIGINAL x with the evaluation at the predictor)."""
+    S = coef.shape[0]
+    n = _plms_args(x, e_c, e_u, coef, S, hist, x_out, pred_x0)
+    _chk(lib().cl_plms_step(x.data_ptr(), e_c.data_ptr(), ptr(e_u), coef.data_ptr(), iteration, S, phase, scale,
+                            hist.data_ptr(), x_out.data_ptr(), ptr(pred_x0), n, stream()), "cl_plms_step")
+    return x_out
+
+
+def plms_step_dev(x, e_c, e_u, coef, cursor, S, scale, hist, x_out, pred_x0=None):
+    """The multistep phase of plms_step with the iteration taken from a device cursor, clamped to [1, S - 1]
+    (hipGraph-replayable): cl_plms_step_dev."""
+    n = _plms_args(x, e_c, e_u, coef, S, hist, x_out, pred_x0)
+    _chk(lib().cl_plms_step_dev(x.data_ptr(), e_c.data_ptr(), ptr(e_u), coef.data_ptr(), cursor.data_ptr(), S, scale,
+                                hist.data_ptr(), x_out.data_ptr(), ptr(pred_x0), n, stream()), "cl_plms_step_dev")
+    return x_out

@@ -479,6 +479,27 @@ int cl_dpmpp_step_dev(const float* x, const float* e_c, const float* e_u, const 
                       float scale, float* hist, float* x_next, float* pred_x0, long n, void* stream);
 int cl_dpm_set_t(const float* coef, const int* cursor, int S, float* ts, int n, void* stream);
 
+/* ---- PLMS (pseudo linear multistep, Liu et al., arXiv:2202.09778), added in ABI 7 (compatible) ----
+ * One sampler update after a model evaluation, as one launch.  coef = DDIM's device [S][4] fp32 table
+ * {a_t, a_prev, sigma_t, sqrt(1-a_t)}; iteration `iter` (0 .. S-1) uses row S-1-iter.  hist = device [4][n] fp32 ring: the
+ * guided eps of iteration k lives in slot k % 4.  e = e_u ? e_u + scale (e_c - e_u) : e_c, and upd(x, e') is
+ *   pred_x0 = (x - sqrt(1-a_t) e') / sqrt(a_t)        x_prev = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma_t^2) e'
+ * phase 0, multistep (iter >= 1): hist[iter % 4] = e; with o_j = hist[(iter - j) % 4],
+ *     e' = (3 e - o1) / 2  |  (23 e - 16 o1 + 5 o2) / 12  |  (55 e - 59 o1 + 37 o2 - 9 o3) / 24   for iter = 1 | 2 | >= 3;
+ *     x_out, pred_x0 = upd(x, e').  A slot that is not part of the order is not read.
+ * phase 1, start (iter == 0): hist[0] = e; x_out = upd(x, e).x_prev, the predictor; pred_x0 is not written.  x_out must not be
+ *     x (phase 2 needs the iteration's input): pointer equality is refused.
+ * phase 2, finish the start (iter == 0): e_c / e_u are the evaluation at (predictor, t_next) and x is the iteration's ORIGINAL
+ *     input; e' = (hist[0] + e) / 2; hist is not written; x_out, pred_x0 = upd(x, e').
+ * x_out may alias x in phases 0 and 2; pred_x0 may be NULL.  cl_plms_step_dev is phase 0 with iter = clamp(*cursor, 1, S-1), so
+ * that the step replays as a hipGraph (time: cl_ddim_set_t, cursor: cl_tick); both run the same device code and give the same
+ * bits.  Refused (1), before anything is launched: S < 1 (S < 2 for _dev), iter outside [0, S), phase outside 0..2, phase 1 or 2
+ * with iter != 0, phase 0 with iter == 0, a null x / e_c / coef / hist / x_out / cursor, n < 0.  n == 0 is CL_OK. */
+int cl_plms_step(const float* x, const float* e_c, const float* e_u, const float* coef, int iter, int S, int phase,
+                 float scale, float* hist, float* x_out, float* pred_x0, long n, void* stream);
+int cl_plms_step_dev(const float* x, const float* e_c, const float* e_u, const float* coef, const int* cursor, int S,
+                     float scale, float* hist, float* x_out, float* pred_x0, long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

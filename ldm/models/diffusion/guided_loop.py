@@ -1,12 +1,12 @@
-"""What DDIMSampler (cldm/ddim_hacked.py) and DPMSolverSampler (dpm_solver/sampler.py) share: how two conditionings become one
-batch, one classifier-free-guidance evaluation, the scopes around a sampling loop (context K/V cache, hint encode) and the
-protocol that captures one step as a hipGraph and replays it.  The samplers keep what differs: tables, update kernels, the
-eager loops and their public API."""
+"""What DDIMSampler (cldm/ddim_hacked.py), DPMSolverSampler (dpm_solver/sampler.py) and PLMSSampler (plms.py) share: how two
+conditionings become one batch, one classifier-free-guidance evaluation, the scopes around a sampling loop (context K/V cache,
+hint encode) and the protocol that captures one step as a hipGraph and replays it.  The samplers keep what differs: tables,
+update kernels, the eager loops and their public API."""
 import contextlib
 
 import torch
 
-# Order of the halves of a batched guidance call.  DDIM sampling batches [cond; uncond]; DDIM inversion and DPM-Solver++ batch
+# Order of the halves of a batched guidance call.  DDIM sampling batches [cond; uncond]; DDIM inversion, DPM-Solver++ and PLMS batch
 # [uncond; cond] as the reference does.  The halves are independent samples, but the order sets the rows of every GEMM and
 # with them possibly the bits, so each path keeps the order it has always had.
 COND_FIRST, UNCOND_FIRST = "cond_first", "uncond_first"

@@ -35,9 +35,10 @@ def get_parser():
     p.add_argument("--strength", type=float, default=1.0, help="strength of controlnet")
     p.add_argument("--cfg", type=float, default=7.5, help="unconditional guidance scale")
     p.add_argument("--empty_prompt", action="store_true", default=False, help="experimental: use empty prompt")
-    p.add_argument("--sampler", type=str, choices=["ddim", "dpm"], default="ddim",
-                   help="ddim (the reference script's sampler) or dpm: DPM-Solver++ (multistep, order 2), which takes "
-                        "--ddim_steps as its number of steps (20 is usual) and ignores --ddim_eta")
+    p.add_argument("--sampler", type=str, choices=["ddim", "dpm", "plms"], default="ddim",
+                   help="ddim (the reference script's sampler); dpm: DPM-Solver++ (multistep, order 2), which takes "
+                        "--ddim_steps as its number of steps (20 is usual) and ignores --ddim_eta; or plms: the pseudo "
+                        "linear multistep sampler on DDIM's schedule, which needs --ddim_eta 0")
     return p
 
 
@@ -89,6 +90,9 @@ def make_sampler(model, name="ddim"):
     if name == "dpm":
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler
         return DPMSolverSampler(model)
+    if name == "plms":
+        from ldm.models.diffusion.plms import PLMSSampler
+        return PLMSSampler(model)
     from cldm.ddim_hacked import DDIMSampler
     return DDIMSampler(model)
 

@@ -1,6 +1,6 @@
 """DDIM with 50 steps against DPM-Solver++ with 20 at the benchmark's DDIM shape (B = 16, CFG 7.5, latent 64, SD1.5 width, bf16).
 
-    python tools/bench_sampler.py [--rounds 5] [--ddim-steps 50] [--dpm-steps 20] [--out FILE]
+    python tools/bench_sampler.py [--rounds 5] [--ddim-steps 50] [--dpm-steps 20] [--plms-steps 0] [--out FILE]
 
 Both legs sample from the same model with the same tensors through one sample() call each, as a one-shot user pays it:
 the first step eager, the second captured as a hipGraph, the rest replayed (neither leg keeps a graph across calls: the
@@ -9,7 +9,8 @@ headline).  A call ends in a device synchronise and is timed with the host clock
 timed length, then alternate round by round so that clock drift hits both; the medians are reported.  ms per step is
 ms per batch over the number of steps, so it carries each leg's share of the eager step and the capture.  One JSON line;
 a missing GPU is an error, not a fallback.  Whether 20 DPM-Solver++ steps match the quality of 50 DDIM steps is the
-solver paper's claim (arXiv:2211.01095), not something this tool measures.
+solver paper's claim (arXiv:2211.01095), not something this tool measures.  --plms-steps N > 0 adds a PLMS leg of N steps
+(N + 1 model evaluations: its first iteration makes two, both eager) to the same rounds; 0, the default, leaves it out.
 """
 import argparse
 import json
@@ -29,6 +30,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--dpm-steps", type=int, default=20)
+    ap.add_argument("--plms-steps", type=int, default=0, help="add a PLMS leg of this many steps (0: none)")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--tiny", action="store_true", help="narrow model: a rehearsal of the tool, not a measurement")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON line to this file")
@@ -48,6 +50,9 @@ def main(argv=None):
     unc = {"c_concat": [hint], "c_crossattn": [torch.randn(B, 77, cd, generator=g).cuda()]}
     x_T = torch.randn(B, 4, H, H, generator=g).cuda()
     legs = {"ddim": (DDIMSampler(model), a.ddim_steps), "dpm": (DPMSolverSampler(model), a.dpm_steps)}
+    if a.plms_steps > 0:
+        from ldm.models.diffusion.plms import PLMSSampler
+        legs["plms"] = (PLMSSampler(model), a.plms_steps)
 
     def run(name):
         sampler, S = legs[name]
@@ -75,6 +80,9 @@ def main(argv=None):
                          min_ms_per_batch=round(ts[0] * 1e3, 2), max_ms_per_batch=round(ts[-1] * 1e3, 2))
     res["dpm_over_ddim_batch_time"] = round(res["dpm"]["ms_per_batch"] / res["ddim"]["ms_per_batch"], 4)
     res["dpm_over_ddim_step_time"] = round(res["dpm"]["ms_per_step"] / res["ddim"]["ms_per_step"], 4)
+    if "plms" in legs:
+        res["plms_over_ddim_batch_time"] = round(res["plms"]["ms_per_batch"] / res["ddim"]["ms_per_batch"], 4)
+        res["plms_over_ddim_step_time"] = round(res["plms"]["ms_per_step"] / res["ddim"]["ms_per_step"], 4)
     line = json.dumps(res)
     print(line)
     if a.out:
