@@ -63,6 +63,10 @@ int cl_debug_attention_last_launch(int* out16) {
 int cl_debug_groupnorm_form(int three_pass, int one_pass) {
   g_gn_three_pass = three_pass ? 1 : 0; g_gn_one_pass = one_pass ? 1 : 0; return CL_OK;
 }
+int cl_debug_groupnorm_group(int mode) {
+  if (mode != 0 && mode != 1 && mode != 2 && mode != 5 && mode != 6) return CL_EINVAL;
+  g_gn_group = mode; return CL_OK;
+}
 int cl_debug_norm_last_launch(int* out12) {
   static_assert(sizeof(NormLaunchRec) == 12 * sizeof(int), "cl_debug_norm_last_launch: twelve ints");
   if (!out12) return CL_EINVAL;

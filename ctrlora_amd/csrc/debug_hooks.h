@@ -22,9 +22,15 @@ int cl_debug_attention_last_launch(int* out16);
 /* GroupNorm launch forms: three_pass = 1 forces partial -> finalize -> apply; one_pass = 0 disables the one-launch
  * register-resident form (defaults 0, 1) */
 int cl_debug_groupnorm_form(int three_pass, int one_pass);
+/* The one-launch form with one workgroup per (sample, group) (csrc/norm.hip gng_*; bf16 only): 0 = never, 1 (default) = where the
+ * shape rule takes it, 2 = whenever the slab fits the register budget (tests at small shapes); 5 / 6 = 1 / 2 with workgroup ids
+ * mapped to (sample, group) pairs in plain order (timing aid: does the XCD placement matter?).  Off in any mode while
+ * cl_debug_groupnorm_form asks for three launches or turns the one-launch forms off.  The probe reports form 5 with NV = vectors
+ * per lane and operand, vectors per pixel row, threads per workgroup, C / G, grid B * G.  Other codes: CL_EINVAL, nothing changes. */
+int cl_debug_groupnorm_group(int mode);
 /* Read-only: what the last normalisation entry point of this process launched (csrc/norm.h: NormLaunchRec; host side only, no
  * GPU touched).  out[0..11] = kind (0 nothing: the call was refused, 1 / 2 GroupNorm forward / backward, 3 / 4 LayerNorm forward /
- * backward), form (1 one launch, 2 two launches, 3 three launches, 4 cooperative; LayerNorm backward: 2 = with the finishing
+ * backward), form (1 one launch, 2 two launches, 3 three launches, 4 cooperative, 5 one launch with one workgroup per (sample, group); LayerNorm backward: 2 = with the finishing
  * kernel), dtype, NV (16-byte vectors per lane kept in registers; 0 for the chunked GroupNorm forms), LPR of the one-launch
  * GroupNorm / PY of the chunked ones / rows per wave iteration of the LayerNorm backward, waves (one-launch GroupNorm) or threads
  * per workgroup, CB (one-launch GroupNorm) / VX (chunked) / D / 8 (LayerNorm), pixel chunks per sample, grid x, grid y,

@@ -5,7 +5,8 @@
 namespace cl {
 
 extern int g_gn_three_pass;   // A/B hook: 1 = partial -> finalize -> apply for every GroupNorm
-extern int g_gn_one_pass;     // A/B hook: 0 = never the one-launch register-resident form
+extern int g_gn_one_pass;     // A/B hook: 0 = never the one-launch register-resident forms
+extern int g_gn_group;        // one workgroup per (sample, group): 0 never, 1 by rule (default), 2 whenever the slab fits; + 4 = naive id mapping
 
 struct GnArgs {
   const void* x; long ldx;      // [B*HW, C] token-major (NHWC), row stride ldx
@@ -44,15 +45,16 @@ struct LnBwdArgs {
 // entry point that refuses its arguments, or whose launch fails (CL_ELAUNCH), leaves kind = 0.  No kernel, launch or argument
 // depends on it.
 enum { NORM_GN_FWD = 1, NORM_GN_BWD = 2, NORM_LN_FWD = 3, NORM_LN_BWD = 4 };
-enum { NORM_FORM_ONE = 1, NORM_FORM_TWO = 2, NORM_FORM_THREE = 3, NORM_FORM_COOP = 4 };
+enum { NORM_FORM_ONE = 1, NORM_FORM_TWO = 2, NORM_FORM_THREE = 3, NORM_FORM_COOP = 4, NORM_FORM_GROUP = 5 };
 struct NormLaunchRec {
   int kind;          // 0 nothing launched (refused), NORM_GN_* / NORM_LN_*
   int form;          // NORM_FORM_*: launches of the call (LayerNorm backward: 2 = kernel + ln_bwd_finish_kernel)
   int dtype;
-  int nv;            // 16-byte vectors per lane held in registers (gn1_* / ln_*; 0 for the chunked GroupNorm forms)
-  int lpr_rpi;       // gn1_*: lanes per pixel row; chunked GroupNorm: PY; LayerNorm: rows per wave iteration
+  int nv;            // 16-byte vectors per lane held in registers (gn1_* / ln_*; 0 for the chunked GroupNorm forms); gng_*: vectors of
+                     // gcd(16, C / G * 2) bytes per lane and operand
+  int lpr_rpi;       // gn1_*: lanes per pixel row; gng_*: vectors per pixel row; chunked GroupNorm: PY; LayerNorm: rows per wave iteration
   int threads;       // gn1_*: waves per workgroup; every other form: threads per workgroup
-  int cb_vx;         // gn1_*: channels per block CB; chunked GroupNorm: VX; LayerNorm: D / 8
+  int cb_vx;         // gn1_*: channels per block CB; gng_*: channels per workgroup C / G; chunked GroupNorm: VX; LayerNorm: D / 8
   int chunks;        // pixel chunks per sample (chunked GroupNorm forms)
   int grid_x, grid_y;
   int colsum;        // dgamma / dbeta of the LayerNorm backward: 0 none, 1 workspace + finish, 2 atomics

@@ -7,6 +7,7 @@
 //                   -> gn_finalize (per-(b,group) mean/rstd, per-(b,channel) scale/shift)
 //                   -> gn_apply   (y = silu?(x*scale + shift))
 //   GroupNorm bwd : gn_bwd_partial -> gn_bwd_finalize (+ dgamma/dbeta) -> gn_bwd_apply
+//   one launch    : gn1_* (sample, channel block) and gng_* (sample, group) keep their slab in registers
 //   LayerNorm     : one wave per row, row kept in registers (D <= 2048)
 //
 // Reference ops replaced: ResBlock in_layers[0:2]/out_layers[0:2]
@@ -569,6 +570,314 @@ static void gn1_bwd_launch(const GnBwdArgs& a, const Gn1Geom& g, hipStream_t st)
 #undef GN1B
 }
 
+// ------------------------------------------------------------------ one-launch GroupNorm, one workgroup per (sample, group)
+// gn1_* needs channel blocks of whole 16-byte vectors (CB = lcm(C / G, 8)): at C = 320 / 640 that quarters / halves its grid and
+// leaves 3 of every 8 lanes idle.  Here ONE workgroup owns ONE (sample, group) pair -- B * G workgroups, 256 at B = 8, G = 32,
+// one per CU -- and keeps the pair's [HW][C / G] slab (the backward: x and dy) in registers between the statistics and the
+// apply: the tensor is read once and written once by one launch, and no workgroup waits for another.  A row segment of a
+// group is C / G * 2 bytes (bf16 only), aligned to VW * 4 = gcd(16, C / G * 2) bytes and no more, so the vectors are 4, 8 or
+// 16 bytes: VPR = segment / vector of them per pixel row.  The (pixel, vector) index is flattened over the lanes,
+// idx = tid + i * threads, with threads = 64 * NW a multiple of VPR: no lane is idle and every lane keeps ONE vector position
+// v = tid % VPR, hence 2 * VW channels whose coefficients it holds in registers.  The whole workgroup is one group, so the
+// statistics are two workgroup-wide sums: fp32 per lane and channel (chains of at most NV terms), then fp64 in a fixed order
+// (xor tree over the lanes, the waves in sequence) and the fp64 finalisation of gn1_fwd_kernel.  Trainable norms reduce the
+// per-channel sums through LDS in a fixed order and add them with one float atomic per channel and sample, as gn1_bwd_kernel.
+//
+// Budget: NW <= 16 waves, i.e. up to 1024 threads = 4 waves per SIMD = 128 VGPRs per lane (VPR = 5 or 15 at the SD1.5 widths
+// gives NW = 15, 960 threads).  Of those the slab may take GNG_FWD_DW = GNG_BWD_DW = 64 dwords (the backward: x and dy
+// together; at 88 the compiler spills); tests/test_gpu_groupnorm_group.py compiles the listing and asserts no scratch, no
+// spills and 4 waves per SIMD.  So the forward holds up to 61440 vectors ([8, 960, 4096]: 240 KB of 491 KB of registers), the
+// backward up to [8, 1920, 1024] (240 KB); the backward of C = 640 / 960 at 64x64 (320 / 480 KB) does not fit and stays on
+// the two-launch form.  NV, the vectors per lane and operand, is one of 6, 16, 22, 64; the backward stops at GNG_BWD_NV = 16:
+// at [8, 320, 4096] (22 four-byte vectors of x, dy and accum each) it was 2 us faster than the two-launch form on buffers
+// that stay in the Infinity Cache and 10 us slower from HBM (profiles/gn_group), so that class is left where it was.
+//
+// The rule (mode 1) takes a shape with HW >= GNG_MIN_HW and B * G >= GNG_MIN_WG workgroups whose slab fits: every class of
+// the SD1.5 step at B = 8 from 16x16 to 64x64 measured faster than gn1_* / the two-launch form by more than the spread of
+// repeated medians, the backward classes above excepted.  Below 192 workgroups gn1_* keeps its shapes.
+//
+// Workgroups are dealt to the 8 XCDs round-robin by linear id.  Neighbouring groups of a sample share 128-byte lines (a
+// segment is 20 bytes at C = 320), so where B * G is a multiple of 8 the ids are mapped such that one XCD gets a contiguous
+// run of (sample, group) pairs and neighbours are adjacent in id (B = 8: sample = id % 8, group = id / 8): a line is then
+// fetched into one L2, and the partial-line stores of neighbours meet there.
+static constexpr int GNG_MAX_WAVES = 16, GNG_FWD_DW = 64, GNG_BWD_DW = 64, GNG_MAX_CG = 128;
+static constexpr int GNG_BWD_NV = 16, GNG_MIN_HW = 256, GNG_MIN_WG = 192;
+int g_gn_group = 1;   // cl_debug_groupnorm_group: 0 never, 1 by rule, 2 whenever the slab fits; + 4 = naive id mapping
+
+struct GngGeom { int cg, VW, VPR, NW, NV, remap; bool ok; };
+
+static GngGeom gng_geom(int B, int HW, int C, int G, bool bwd) {
+  GngGeom g{}; g.ok = false;
+  const int mode = g_gn_group & 3;
+  if (!mode || !g_gn_one_pass || g_gn_three_pass || C % G) return g;
+  const int cg = C / G;
+  if ((cg & 1) || cg > GNG_MAX_CG) return g;
+  if (mode == 1 && (HW < GNG_MIN_HW || (long)B * G < GNG_MIN_WG)) return g;
+  g.cg = cg;
+  g.VW = cg % 8 == 0 ? 4 : cg % 4 == 0 ? 2 : 1;      // dwords per vector: gcd(16, cg * 2) / 4
+  g.VPR = cg / (2 * g.VW);
+  int nw = GNG_MAX_WAVES;
+  while (nw > 0 && (64 * nw) % g.VPR) --nw;
+  if (!nw) return g;
+  g.NW = nw;
+  const long total = (long)HW * g.VPR, T = 64 * nw;
+  const long nv = (total + T - 1) / T;
+  g.NV = nv <= 6 ? 6 : nv <= 16 ? 16 : nv <= 22 ? 22 : nv <= 64 ? 64 : 0;
+  if (!g.NV || g.NV * g.VW * (bwd ? 2 : 1) > (bwd ? GNG_BWD_DW : GNG_FWD_DW) || (bwd && g.NV > GNG_BWD_NV)) return g;
+  g.remap = !(g_gn_group & 4) && ((long)B * G) % 8 == 0;
+  g.ok = true;
+  return g;
+}
+
+template <int VW> __device__ __forceinline__ void gng_ld(const bf16_t* p, uint32_t* d) {
+  if constexpr (VW == 4) { const uint4 r = *reinterpret_cast<const uint4*>(p); d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w; }
+  else if constexpr (VW == 2) { const uint2 r = *reinterpret_cast<const uint2*>(p); d[0] = r.x; d[1] = r.y; }
+  else d[0] = *reinterpret_cast<const uint32_t*>(p);
+}
+template <int VW> __device__ __forceinline__ void gng_get(const uint32_t* d, float* f) {
+#pragma unroll
+  for (int j = 0; j < VW; ++j) { f[2 * j] = __uint_as_float(d[j] << 16); f[2 * j + 1] = __uint_as_float(d[j] & 0xffff0000u); }
+}
+template <int VW> __device__ __forceinline__ void gng_st(bf16_t* p, const float* f) {
+  if constexpr (VW == 4) {
+    uint4 r; r.x = pack2bf(f[0], f[1]); r.y = pack2bf(f[2], f[3]); r.z = pack2bf(f[4], f[5]); r.w = pack2bf(f[6], f[7]);
+    *reinterpret_cast<uint4*>(p) = r;
+  } else if constexpr (VW == 2) {
+    uint2 r; r.x = pack2bf(f[0], f[1]); r.y = pack2bf(f[2], f[3]);
+    *reinterpret_cast<uint2*>(p) = r;
+  } else *reinterpret_cast<uint32_t*>(p) = pack2bf(f[0], f[1]);
+}
+
+// Between the statistics and the apply pass the slab stays PACKED: without this the compiler keeps the unpacked floats of the
+// first pass alive for the second (common subexpressions), which doubles the registers of the slab.  Emits no instruction.
+template <int NV, int VW> __device__ __forceinline__ void gng_keep_packed(uint32_t (&d)[NV][VW]) {
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+#pragma unroll
+    for (int j = 0; j < VW; ++j) asm volatile("" : "+v"(d[i][j]));
+  }
+}
+
+// the (sample, group) pair of this workgroup
+__device__ __forceinline__ void gng_owner(int B, int G, int remap, int& b, int& g) {
+  int id = blockIdx.x;
+  if (remap) id = (id & 7) * ((B * G) >> 3) + (id >> 3);
+  b = id / G; g = id - b * G;
+}
+
+// workgroup-wide sums of two doubles in a fixed order (xor tree over the lanes, then the waves in sequence); valid in every thread
+__device__ __forceinline__ void gng_block_sum2(double& a, double& b, double (*red)[GNG_MAX_WAVES]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][wave] = a; red[1][wave] = b; }
+  __syncthreads();
+  a = 0; b = 0;
+  for (int w = 0; w < nw; ++w) { a += red[0][w]; b += red[1][w]; }
+}
+
+template <bool SILU, int VW, int NV>
+__global__ __launch_bounds__(1024) void gng_fwd_kernel(const bf16_t* __restrict__ x, long ldx, bf16_t* __restrict__ y, long ldy,
+                                                        int B, int HW, int G, int cg, int VPR, int remap, float eps,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        float* __restrict__ stats) {
+  constexpr int EPV = 2 * VW;
+  __shared__ double red[2][GNG_MAX_WAVES];
+  int b, g; gng_owner(B, G, remap, b, g);
+  const int tid = threadIdx.x, PL = blockDim.x / VPR;
+  const int p0 = tid / VPR, v = tid - p0 * VPR, c0 = g * cg + v * EPV;
+  int cnt = p0 < HW ? (HW - p0 + PL - 1) / PL : 0;           // this lane's pixels: p0, p0 + PL, ...
+  // every load is issued, straight-line: slots past the lane's last pixel re-read that pixel (a lane without pixels: the
+  // sample's last row), in bounds and served by L1, and count for nothing below
+  const bf16_t* xp = x + ((long)b * HW + min(p0, HW - 1)) * ldx + c0;
+  const long xs = (long)PL * ldx;
+  uint32_t d[NV][VW];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) { gng_ld<VW>(xp, d[i]); if (i + 1 < cnt) xp += xs; }
+  asm volatile("" : "+v"(cnt));            // the NV comparisons with cnt are made again in every pass, not kept in scalar registers
+  float s[EPV], q[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) { s[e] = 0.f; q[e] = 0.f; }
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    if (i < cnt) {
+      float f[EPV]; gng_get<VW>(d[i], f);
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) { s[e] += f[e]; q[e] += f[e] * f[e]; }
+    }
+  double S = 0, Q = 0;
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) { S += s[e]; Q += q[e]; }
+  gng_block_sum2(S, Q, red);
+  const double n = (double)HW * cg, mean = S / n;
+  double var = Q / n - mean * mean;
+  if (var < 0) var = 0;
+  const float mean_f = (float)mean, rstd_f = (float)(1.0 / sqrt(var + (double)eps));
+  if (tid == 0) { stats[((long)b * G + g) * 2] = mean_f; stats[((long)b * G + g) * 2 + 1] = rstd_f; }
+  gng_keep_packed<NV, VW>(d);
+  asm volatile("" : "+v"(cnt));
+  float sc[EPV], sh[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) {
+    const double scd = (double)rstd_f * (double)gamma[c0 + e];
+    sc[e] = (float)scd;
+    sh[e] = (float)((double)beta[c0 + e] - (double)mean_f * scd);
+  }
+  bf16_t* yp = y + ((long)b * HW + p0) * ldy + c0;
+  const long ys = (long)PL * ldy;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    if (i < cnt) {
+      float f[EPV]; gng_get<VW>(d[i], f);
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const float z = f[e] * sc[e] + sh[e];
+        f[e] = SILU ? silu_f(z) : z;
+      }
+      gng_st<VW>(yp, f); yp += ys;
+    }
+}
+
+// per-channel totals of one quantity over the workgroup's pixels, added onto dst[0 .. cg) with one float atomic per channel.
+// Lane t holds val[e] for channel (t % VPR) * EPV + e; lsum is [EPV][threads], lpart [cg][8].  Fixed order: deterministic.
+template <int EPV>
+__device__ __forceinline__ void gng_channel_atomics(const float* val, int cg, int VPR, float* lsum, float* lpart, float* dst) {
+  const int tid = threadIdx.x, T = blockDim.x, PL = T / VPR;
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) lsum[e * T + tid] = val[e];
+  __syncthreads();
+  for (int i = tid; i < cg * 8; i += T) {
+    const int cl = i >> 3, v = cl / EPV, e = cl - v * EPV;
+    float a = 0.f;
+    for (int j = i & 7; j < PL; j += 8) a += lsum[e * T + v + VPR * j];
+    lpart[i] = a;
+  }
+  __syncthreads();
+  if (tid < cg) {
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a += lpart[tid * 8 + j];
+    atomicAdd(dst + tid, a);
+  }
+}
+
+template <bool SILU, int VW, int NV>
+__global__ __launch_bounds__(1024) void gng_bwd_kernel(const bf16_t* __restrict__ x, long ldx, const bf16_t* __restrict__ dy, long lddy,
+                                                        const bf16_t* __restrict__ accum, long ldacc, bf16_t* __restrict__ dx, long lddx,
+                                                        int B, int HW, int G, int cg, int VPR, int remap,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        const float* __restrict__ stats, float* __restrict__ dgamma,
+                                                        float* __restrict__ dbeta) {
+  constexpr int EPV = 2 * VW;
+  __shared__ double red[2][GNG_MAX_WAVES];
+  __shared__ float lsum[EPV * 64 * GNG_MAX_WAVES];
+  __shared__ float lpart[GNG_MAX_CG * 8];
+  int b, g; gng_owner(B, G, remap, b, g);
+  const int tid = threadIdx.x, PL = blockDim.x / VPR;
+  const int p0 = tid / VPR, v = tid - p0 * VPR, c0 = g * cg + v * EPV;
+  int cnt = p0 < HW ? (HW - p0 + PL - 1) / PL : 0;
+  const long row0 = (long)b * HW + min(p0, HW - 1);          // loads past the lane's last pixel: as gng_fwd_kernel
+  const bf16_t* xp = x + row0 * ldx + c0;
+  const bf16_t* dp = dy + row0 * lddy + c0;
+  const long xs = (long)PL * ldx, ds = (long)PL * lddy;
+  uint32_t dxv[NV][VW], ddv[NV][VW];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    gng_ld<VW>(xp, dxv[i]); gng_ld<VW>(dp, ddv[i]);
+    if (i + 1 < cnt) { xp += xs; dp += ds; }
+  }
+  asm volatile("" : "+v"(cnt));
+  const float mu = stats[((long)b * G + g) * 2], rs = stats[((long)b * G + g) * 2 + 1];
+  float ga[EPV], be[EPV], s[EPV], q[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) { ga[e] = gamma[c0 + e]; be[e] = beta[c0 + e]; s[e] = 0.f; q[e] = 0.f; }
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    if (i < cnt) {
+      float f[EPV], d[EPV]; gng_get<VW>(dxv[i], f); gng_get<VW>(ddv[i], d);
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const float xh = (f[e] - mu) * rs;
+        float dz = d[e];
+        if (SILU) dz *= dsilu_f(xh * ga[e] + be[e]);
+        s[e] += dz; q[e] += dz * xh;
+      }
+    }
+  double s1 = 0, s2 = 0;                   // gamma-weighted group sums
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) { s1 += (double)ga[e] * s[e]; s2 += (double)ga[e] * q[e]; }
+  gng_block_sum2(s1, s2, red);
+  if (dgamma) {
+    gng_channel_atomics<EPV>(q, cg, VPR, lsum, lpart, dgamma + g * cg);
+    gng_channel_atomics<EPV>(s, cg, VPR, lsum, lpart, dbeta + g * cg);
+  }
+  gng_keep_packed<NV, VW>(dxv);
+  gng_keep_packed<NV, VW>(ddv);
+  asm volatile("" : "+v"(cnt));
+  const double n = (double)HW * cg, rstd = rs;
+  const float k2 = (float)(rstd * s1 / n), k3 = (float)(rstd * s2 / n);
+  float k1[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) k1[e] = (float)(rstd * ga[e]);
+  bf16_t* op = dx + row0 * lddx + c0;
+  const bf16_t* ap = accum ? accum + row0 * ldacc + c0 : nullptr;
+  const long os = (long)PL * lddx, as = (long)PL * ldacc;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    if (i < cnt) {
+      float f[EPV], d[EPV], ac[EPV]; gng_get<VW>(dxv[i], f); gng_get<VW>(ddv[i], d);
+      if (accum) { uint32_t av[VW]; gng_ld<VW>(ap, av); gng_get<VW>(av, ac); ap += as; }
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const float xh = (f[e] - mu) * rs;
+        float dz = d[e];
+        if (SILU) dz *= dsilu_f(xh * ga[e] + be[e]);
+        float r = dz * k1[e] - k2 - xh * k3;
+        if (accum) r += ac[e];
+        f[e] = r;
+      }
+      gng_st<VW>(op, f); op += os;
+    }
+}
+
+static void gng_rec(int kind, const GngGeom& g, int B, int G) {
+  g_norm_last = NormLaunchRec{kind, NORM_FORM_GROUP, CL_BF16, g.NV, g.VPR, g.NW * 64, g.cg, 0, B * G, 1, 0, 1};
+}
+
+// every (VW, NV) pair the budgets admit: X(VW, NV)
+#define GNG_FWD_FORMS(X) X(1, 6) X(1, 16) X(1, 22) X(1, 64) X(2, 6) X(2, 16) X(2, 22) X(4, 6) X(4, 16)
+#define GNG_BWD_FORMS(X) X(1, 6) X(1, 16) X(2, 6) X(2, 16) X(4, 6)
+
+template <bool SILU>
+static int gng_fwd_launch(const GnArgs& a, const GngGeom& g, hipStream_t st) {
+  const dim3 grid(a.B * a.G), blk(g.NW * 64);
+#define GNG_F(VW_, NV_)                                                                                                          \
+  if (g.VW == VW_ && g.NV == NV_)                                                                                                \
+    hipLaunchKernelGGL((gng_fwd_kernel<SILU, VW_, NV_>), grid, blk, 0, st, (const bf16_t*)a.x, a.ldx, (bf16_t*)a.y, a.ldy, a.B, \
+                       a.HW, a.G, g.cg, g.VPR, g.remap, a.eps, a.gamma, a.beta, a.stats);
+  GNG_FWD_FORMS(GNG_F)
+#undef GNG_F
+  CL_CHECK_LAUNCH();
+  gng_rec(NORM_GN_FWD, g, a.B, a.G);
+  return CL_OK;
+}
+
+template <bool SILU>
+static int gng_bwd_launch(const GnBwdArgs& a, const GngGeom& g, hipStream_t st) {
+  const dim3 grid(a.B * a.G), blk(g.NW * 64);
+#define GNG_B(VW_, NV_)                                                                                                          \
+  if (g.VW == VW_ && g.NV == NV_)                                                                                                \
+    hipLaunchKernelGGL((gng_bwd_kernel<SILU, VW_, NV_>), grid, blk, 0, st, (const bf16_t*)a.x, a.ldx, (const bf16_t*)a.dy,      \
+                       a.lddy, (const bf16_t*)a.accum, a.ldacc, (bf16_t*)a.dx, a.lddx, a.B, a.HW, a.G, g.cg, g.VPR, g.remap,    \
+                       a.gamma, a.beta, a.stats, a.dgamma, a.dbeta);
+  GNG_BWD_FORMS(GNG_B)
+#undef GNG_B
+  CL_CHECK_LAUNCH();
+  gng_rec(NORM_GN_BWD, g, a.B, a.G);
+  return CL_OK;
+}
+
 static bool gn_two_pass_ok(const GnGeom& g, int C, int G) {
   return !g_gn_three_pass && C / 8 == g.VX && G <= 64 && g.threads >= G && g.threads >= 64;
 }
@@ -621,6 +930,10 @@ int gn_fwd(const GnArgs& a, int dtype, hipStream_t st) {
   if (a.C % 8 || a.C % a.G || a.ldx % 8 || a.ldy % 8 || a.C > 8192) return CL_EINVAL;
   if (a.C / 8 > 320 && (a.C / 8) % 320) return CL_EINVAL;  // uniform trip count across the block
   if (gnc_fwd(a, dtype, st) == CL_OK) return CL_OK;        // groups spanning >= 1024 pixels: one launch, one pass (norm_coop.hip)
+  if (dtype == CL_BF16) {                                  // one workgroup per (sample, group), where the rule takes the shape
+    const GngGeom gg = gng_geom(a.B, a.HW, a.C, a.G, false);
+    if (gg.ok) return a.silu ? gng_fwd_launch<true>(a, gg, st) : gng_fwd_launch<false>(a, gg, st);
+  }
   return dtype == CL_BF16 ? gn_fwd_t<bf16_t>(a, st) : gn_fwd_t<float>(a, st);
 }
 
@@ -920,6 +1233,10 @@ int gn_bwd(const GnBwdArgs& a, int dtype, hipStream_t st) {
   if (a.accum && a.ldacc % 8) return CL_EINVAL;
   if ((a.dgamma == nullptr) != (a.dbeta == nullptr)) return CL_EINVAL;
   if (gnc_bwd(a, dtype, st) == CL_OK) return CL_OK;
+  if (dtype == CL_BF16) {
+    const GngGeom gg = gng_geom(a.B, a.HW, a.C, a.G, true);
+    if (gg.ok) return a.silu ? gng_bwd_launch<true>(a, gg, st) : gng_bwd_launch<false>(a, gg, st);
+  }
   return dtype == CL_BF16 ? gn_bwd_t<bf16_t>(a, st) : gn_bwd_t<float>(a, st);
 }
 

@@ -133,6 +133,7 @@ _DEBUG_SIGS = {
     "cl_debug_attention_fuse_delta": [_I],
     "cl_debug_attention_last_launch": [_P],
     "cl_debug_groupnorm_form": [_I, _I],
+    "cl_debug_groupnorm_group": [_I],
     "cl_debug_norm_last_launch": [_P],
     "cl_debug_groupnorm_coop": [_I],
     "cl_debug_groupnorm_coop_timeouts": [],
@@ -168,6 +169,8 @@ def lib():
         gn1 = os.environ.get("CTRLORA_GN_ONE_PASS", "1") != "0"        # A/B switch: one-launch (register-resident) GroupNorm
         if gn3 or not gn1:
             L.cl_debug_groupnorm_form(int(gn3), int(gn1))
+        if os.environ.get("CTRLORA_GN_GROUP", "1") == "0":             # A/B switch: one workgroup per (sample, group) GroupNorm (norm.hip gng_*)
+            L.cl_debug_groupnorm_group(0)
         if os.environ.get("CTRLORA_GN_COOP", "0") == "1":              # A/B switch: cooperative one-pass GroupNorm (norm_coop.hip; off: no faster)
             L.cl_debug_groupnorm_coop(1)
         L.cl_debug_gemm_xs_rules(int(XS_ENABLED))
