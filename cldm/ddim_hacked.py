@@ -7,6 +7,8 @@ What changes underneath, not in the results:
   * classifier-free guidance evaluates the conditional and unconditional passes as one batch of 2B through the
     engine when both conditionings have the same structure (samples are independent, so the results are
     those of the reference's two sequential apply_model calls);
+  * the S-step loops -- sampling, also with mask / x0 (:154-157: one fused HIP launch re-noises the known region and blends),
+    decode (:298-317) and encode (:234-279) -- keep their state on the device and replay one captured step;
   * schedule tables are computed exactly as the reference does (fp64 numpy / fp32 torch on the host) --
     index and timestep bookkeeping is bit-exact.
 """
@@ -39,6 +41,10 @@ class DDIMSampler(object):
         # apply_model call (cldm_ctrlora_inference.py:165-172: 2 x 1.1 TFLOP per image and denoise step), for measurements
         # of the reference-faithful form.
         self.hoist_hint_encode = True
+        # The noise of the forward process in a masked run (mask=, x0=).  None (default): every step draws torch.randn_like(x0),
+        # as the reference's q_sample does.  A tensor of x0's shape: that noise at every step, in the eager and in the replayed
+        # loop alike, which makes the two comparable bit for bit whatever the generator's stream.
+        self.q_noise = None
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -106,17 +112,20 @@ class DDIMSampler(object):
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
-        if (self.use_graph and img.is_cuda and mask is None and ucg_schedule is None and total_steps >= 4
-                and noise_dropout == 0. and callable(getattr(self.model, "engine", None))):
+        if (self.use_graph and img.is_cuda and ucg_schedule is None and total_steps >= 4
+                and noise_dropout == 0. and callable(getattr(self.model, "engine", None))
+                and (mask is None or self._mask_replayable(mask, x0, img))):
             return self._sampling_graphed(cond, img, timesteps, callback, img_callback, log_every_t, temperature,
-                                          unconditional_guidance_scale, unconditional_conditioning, intermediates)
+                                          unconditional_guidance_scale, unconditional_conditioning, intermediates,
+                                          mask=mask, x0=x0)
         with context_kv(engine_of(self.model)):
             for i, step in enumerate(time_range):
                 index = total_steps - i - 1
                 ts = torch.full((b,), int(step), device=device, dtype=torch.long)
                 if mask is not None:
                     assert x0 is not None
-                    img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                    q = self.model.q_sample(x0, ts) if self.q_noise is None else self.model.q_sample(x0, ts, noise=self.q_noise)
+                    img = q * mask + (1. - mask) * img
                 if ucg_schedule is not None:
                     assert len(ucg_schedule) == len(time_range)
                     unconditional_guidance_scale = ucg_schedule[i]
@@ -133,26 +142,61 @@ class DDIMSampler(object):
                     intermediates["pred_x0"].append(pred_x0)
         return img, intermediates
 
+    def _replayable(self, x, steps):
+        """Do decode() / encode() run their loop as a captured, replayed step?  The conditions of ddim_sampling."""
+        return bool(self.use_graph and x.is_cuda and steps >= 4 and callable(getattr(self.model, "engine", None)))
+
+    def _q_tables(self):
+        """The model's fp32 device tables that LatentDiffusion.q_sample reads, or None."""
+        tabs = tuple(getattr(self.model, k, None) for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod"))
+        ok = all(torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32 and v.dim() == 1 and v.is_contiguous() for v in tabs)
+        return tabs if ok and tabs[0].numel() == tabs[1].numel() >= 1 else None
+
+    def _mask_replayable(self, mask, x0, img):
+        """Can the blend of a masked run go into the captured step (cl_qsample_blend)?  x0 given, a mask of one of the layouts
+        (B | 1, C | 1, H, W), the forward-process noise (if fixed) of x0's shape, and a model with the tables of q_sample."""
+        if x0 is None or not torch.is_tensor(x0) or not torch.is_tensor(mask) or self._q_tables() is None:
+            return False
+        if not (x0.is_cuda and mask.is_cuda and x0.shape == img.shape and img.dim() == 4 and mask.dim() == 4):
+            return False
+        if self.q_noise is not None and not (torch.is_tensor(self.q_noise) and self.q_noise.is_cuda and self.q_noise.shape == x0.shape):
+            return False
+        return (tuple(mask.shape[2:]) == tuple(img.shape[2:]) and mask.shape[0] in (1, img.shape[0])
+                and mask.shape[1] in (1, img.shape[1]))
+
     @torch.no_grad()
     def _sampling_graphed(self, cond, img, timesteps, callback, img_callback, log_every_t, temperature, cfg_scale,
-                          uncond, intermediates):
+                          uncond, intermediates, mask=None, x0=None, coef=None, order=COND_FIRST, cat_tensors=False, after=None):
         """The S-step loop of ddim_sampling (:157-178) with the loop state on the DEVICE: a cursor i counts
-        iterations, `cl_ddim_set_t` derives ts = ddim_timesteps[S-1-i] and `cl_ddim_step_dev` the table row, so
-        one step = both CFG passes through the engine + the fused update is a fixed kernel sequence, which
-        guided_loop.run_steps captures once and replays (or, with a kept graph of the same problem, only replays)."""
+        iterations, `cl_ddim_set_t` derives ts = timesteps[S-1-i] and `cl_ddim_step_dev` row S-1-i of the table, so
+        one step = [the masked blend +] both CFG passes through the engine + the fused update is a fixed kernel sequence, which
+        guided_loop.run_steps captures once and replays (or, with a kept graph of the same problem, only replays).
+        mask / x0: a masked run (_mask_replayable); the step opens with cl_qsample_blend at this step's time, in place on x,
+        as the reference blends before the model evaluation (:154-157).  decode() runs its t_start steps here unchanged.
+        encode() passes its own table `coef`, both REVERSED with the times (the cursor walks rows S-1-i), the batching of its
+        eager loop (`order`, `cat_tensors`) and `after(i, x)` in place of the sampling loop's callbacks and intermediates."""
         from ctrlora_amd import hip
         model, device = self.model, img.device
         S, b = int(timesteps.shape[0]), img.shape[0]
+        coef = self.coef_table if coef is None else coef
+        ident = lambda t: None if t is None else (id(t), t._version, tuple(t.shape))
+        q_tabs = self._q_tables() if mask is not None else None
 
         def _sig(c):
             if c is None:
                 return None
+            if torch.is_tensor(c):     # a bare tensor conditioning (DDIM inversion's callers, analytic models)
+                return ident(c)
+            if isinstance(c, (list, tuple)):
+                return tuple(_sig(e) for e in c)
             return tuple((k, tuple((id(t), t._version, tuple(t.shape)) for t in (v if isinstance(v, (list, tuple)) else [v])
                                    if torch.is_tensor(t))) for k, v in sorted(c.items()) if v is not None)
 
         def _plain(c):     # non-tensor entries of a conditioning dict (cond['task'], ...) are baked into the capture too
-            if c is None:
+            if c is None or torch.is_tensor(c):
                 return None
+            if isinstance(c, (list, tuple)):
+                return tuple(_plain(e) for e in c)
             return tuple((k, repr(v)) for k, v in sorted(c.items())
                          if v is not None and not torch.is_tensor(v)
                          and not (isinstance(v, (list, tuple)) and any(torch.is_tensor(t) for t in v)))
@@ -167,23 +211,28 @@ class DDIMSampler(object):
                tuple(float(v) for v in (getattr(model, "lora_weights", None) or ())),
                bool(getattr(model, "only_mid_control", False)), bool(self.batch_cfg), bool(self.hoist_hint_encode), _plain(cond),
                _plain(uncond), WEIGHTS_GENERATION[0],
-               tuple(a.ip_scale for a in model.engine().unet.ip_layers))
+               tuple(a.ip_scale for a in model.engine().unet.ip_layers),
+               # a masked step reads mask, x0, the fixed noise and the two tables of q_sample by address
+               order, bool(cat_tensors), ident(mask), ident(x0), ident(self.q_noise if mask is not None else None),
+               None if q_tabs is None else tuple(ident(t) for t in q_tabs))
 
         def after_step(i):     # x, pred_x0: the device state of the loop that runs (a kept graph's, or a fresh one)
+            if after is not None:
+                return after(i, x)
             if callback:
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
             index = S - i - 1
-            if index % log_every_t == 0 or index == S - 1:
+            if intermediates is not None and (index % log_every_t == 0 or index == S - 1):
                 intermediates["x_inter"].append(x.clone())
                 intermediates["pred_x0"].append(pred_x0.clone())
 
         st = self._graph_state if self.reuse_graph else None
         # sample() rebuilds the coefficient table on every call: the kept graph reads ITS table by address (held in st), so a
         # hit needs equal contents, not the same tensor
-        if (st is not None and st["key"] == key and not (callback or img_callback)
-                and st["coef"].shape == self.coef_table.shape and bool(torch.equal(st["coef"], self.coef_table))):
+        if (st is not None and st["key"] == key and not (callback or img_callback or after)
+                and st["coef"].shape == coef.shape and bool(torch.equal(st["coef"], coef))):
             # replay-only loop: same kernels, same buffers (the context K/V products of iteration 0 are still in st)
             x, pred_x0 = st["x"], st["pred_x0"]
             x.copy_(img.float())
@@ -198,26 +247,33 @@ class DDIMSampler(object):
         cursor = torch.zeros(1, dtype=torch.int32, device=device)
         table = torch.as_tensor(np.ascontiguousarray(timesteps).astype(np.int64)).to(device)
         guide = None if cfg_scale == 1. else uncond      # None: no guidance, one pass
-        both = batch_conds(cond, guide, COND_FIRST, cat_tensors=False) if self.batch_cfg else None
-        any_sigma = bool((self.coef_table[:, 2] != 0).any())
+        both = batch_conds(cond, guide, order, cat_tensors=cat_tensors) if self.batch_cfg or cat_tensors else None
+        any_sigma = bool((coef[:, 2] != 0).any())
+        if mask is not None:
+            mask_f, x0_f = mask.float().contiguous(), x0.float().contiguous()
+            q_fixed = None if self.q_noise is None else self.q_noise.float().contiguous()
 
         def body():
             hip.ddim_set_t(table, cursor, S, ts)
-            e_c, e_u = guided_eps(model, x, ts, cond, guide, both, COND_FIRST)
+            if mask is not None:
+                # the reference's order: q_sample's draw, then (eta > 0) the draw of the update
+                hip.qsample_blend(x0_f, torch.randn_like(x0_f) if q_fixed is None else q_fixed, ts, q_tabs[0], q_tabs[1], mask_f, x, x)
+            e_c, e_u = guided_eps(model, x, ts, cond, guide, both, order)
             # the reference draws the sigma*noise term every step (:227); with eta = 0 every sigma is zero and
             # the draw cannot change the sample, so it is skipped (only the global RNG position differs)
             noise = noise_like(x.shape, device, False) * temperature if any_sigma else None
             hip.ddim_step_dev(x, e_c.float().contiguous(), None if e_u is None else e_u.float().contiguous(), noise,
-                              self.coef_table, cursor, S, float(cfg_scale), x, pred_x0)
+                              coef, cursor, S, float(cfg_scale), x, pred_x0)
             hip.tick(cursor)
 
         with context_kv(model.engine()) as eng:
-            graph = run_steps(body, S, after_step, keep_graph=self.reuse_graph)
+            graph = run_steps(body, S, after_step, keep_graph=self.reuse_graph and after is None)
             kv_keep = eng.detach_context_cache() if graph is not None else None
         if graph is not None:
             # the graph reads the cached K/V products and the conditioning tensors by address: hold them
             self._graph_state = dict(key=key, graph=graph, x=x, pred_x0=pred_x0, ts=ts, cursor=cursor, table=table, kv=kv_keep,
-                                     conds=(cond, uncond, both), coef=self.coef_table,
+                                     conds=(cond, uncond, both), coef=coef,
+                                     masked=None if mask is None else (mask, x0, self.q_noise, mask_f, x0_f, q_fixed, q_tabs),
                                      eng=eng)     # keeps id(engine) in `key` from being recycled by a rebuilt engine
         return x.clone(), intermediates
 
@@ -276,6 +332,24 @@ class DDIMSampler(object):
         uc = None if unconditional_guidance_scale == 1. else unconditional_conditioning
         assert uc is not None or unconditional_guidance_scale == 1.
         both = batch_conds(c, uc, UNCOND_FIRST, cat_tensors=True)
+
+        def keep(i, x_i, live=False):     # live: x_i is the loop's own buffer, the next step overwrites it
+            if return_intermediates and ((i % every == 0 and i < n - 1) or i >= n - 2):
+                kept.append(x_i.clone() if live else x_i)
+                kept_at.append(i)
+            if callback:
+                callback(i)
+
+        if self._replayable(x, n) and not use_original_steps:
+            # the same update on the device cursor: it walks rows S-1-i, so it gets the times and the table reversed
+            with hint_scope(self.model, self.hoist_hint_encode):
+                x, _ = self._sampling_graphed(c, x, np.ascontiguousarray(steps_all[:n][::-1]), None, None, 1, 1., unconditional_guidance_scale,
+                                              uc, None, coef=table.flip(0).contiguous(), order=UNCOND_FIRST, cat_tensors=True,
+                                              after=lambda i, x_i: keep(i, x_i, live=True))
+            out = {"x_encoded": x, "intermediate_steps": kept_at}
+            if return_intermediates:
+                out.update({"intermediates": kept})
+            return x, out
         for i in range(n):
             t = torch.full((b,), int(steps_all[i]), device=self.model.device, dtype=torch.long)
             e_c, e_u = guided_eps(self.model, x, t, c, uc, both, UNCOND_FIRST)
@@ -283,11 +357,7 @@ class DDIMSampler(object):
             hip.ddim_step(x, e_c.float().contiguous(), None if e_u is None else e_u.float().contiguous(), None, table, i,
                           float(unconditional_guidance_scale), x_new, None)
             x = x_new
-            if return_intermediates and ((i % every == 0 and i < n - 1) or i >= n - 2):
-                kept.append(x)
-                kept_at.append(i)
-            if callback:
-                callback(i)
+            keep(i, x)
         out = {"x_encoded": x, "intermediate_steps": kept_at}
         if return_intermediates:
             out.update({"intermediates": kept})
@@ -323,6 +393,12 @@ class DDIMSampler(object):
         timesteps = self.ddim_timesteps[:t_start]
         total_steps = timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
+        if self._replayable(x_latent, total_steps):
+            # rows S-1-i of the first t_start rows of the table are what the device cursor reads with S = t_start
+            with hint_scope(self.model, self.hoist_hint_encode):
+                x_dec, _ = self._sampling_graphed(cond, x_latent, timesteps, callback, None, 1, 1., unconditional_guidance_scale,
+                                                  unconditional_conditioning, None)
+            return x_dec
         x_dec = x_latent
         for i, step in enumerate(np.flip(timesteps)):
             index = total_steps - i - 1

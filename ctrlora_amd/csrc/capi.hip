@@ -345,6 +345,7 @@ int cl_gather_rows(int dtype, const void* src, long lds_, const long* rows, void
 int cl_repack(int dtype, const float* flat, const long* desc, const int* tile_prefix, int ndesc, int total_tiles, void* stream) { return repack(dtype, flat, desc, tile_prefix, ndesc, total_tiles, S(stream)); }
 int cl_timestep_embedding(int dtype, const long* t, const float* freqs, void* out, long ldo, int B, int half, void* stream) { return timestep_embed(dtype, t, freqs, out, ldo, B, half, S(stream)); }
 int cl_qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac, float* out, int B, long per_sample, void* stream) { return qsample(z, noise, t, sqrt_ac, sqrt_1mac, out, B, per_sample, S(stream)); }
+int cl_qsample_blend(const float* x0, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac, int T, const float* mask, int mask_per_batch, int mask_per_channel, const float* x, float* out, int B, int C, long HW, void* stream) { return qsample_blend(x0, noise, t, sqrt_ac, sqrt_1mac, T, mask, mask_per_batch, mask_per_channel, x, out, B, C, HW, S(stream)); }
 int cl_posterior_sample_pair(const float* mom_a, const float* e_a, float* out_a, const float* mom_b, const float* e_b, float* out_b, int B, long per_sample, float scale, void* stream) { return posterior_sample_pair(mom_a, e_a, out_a, mom_b, e_b, out_b, B, per_sample, scale, S(stream)); }
 int cl_mse_loss(const float* eps, const float* target, float* d_eps, float* loss, long n, float gscale, void* stream) { return mse_loss(eps, target, d_eps, loss, n, gscale, S(stream)); }
 int cl_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef, int index, float scale, float* x_prev, float* pred_x0, long n, void* stream) { return ddim_step(x, e_c, e_u, noise, coef, index, scale, x_prev, pred_x0, n, S(stream)); }

@@ -8,13 +8,15 @@ namespace cl {
 // Every launcher resets it on entry and ew_done() (elementwise.hip) writes it after the launch check, so a refused or failed
 // call leaves id = 0.  form / aux: colsum 1 = block partials + finishing kernel, 2 = atomics, aux = pixel chunks; zero: bit 0 =
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
-// transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2).
+// transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
+// qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
   EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
-  EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV
+  EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV,
+  EW_QSAMPLE_BLEND
 };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
@@ -38,6 +40,10 @@ int timestep_embed(int dtype, const long* t, const float* freqs, void* out, long
 int timestep_embed_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, hipStream_t st);
 int qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
             float* out, int B, long per, hipStream_t st);
+// q_sample(x0, t) * mask + (1 - mask) * x of a masked sampling step in one launch; out may be x (elementwise.hip)
+int qsample_blend(const float* x0, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac, int T,
+                  const float* mask, int mask_per_batch, int mask_per_channel, const float* x, float* out, int B, int C, long HW,
+                  hipStream_t st);
 // scale * (mean + std * e) of one or two cached posteriors in one launch (LatentDiffusion.get_first_stage_encoding)
 int posterior_sample_pair(const float* mom_a, const float* e_a, float* out_a, const float* mom_b, const float* e_b, float* out_b,
                           int B, long per, float scale, hipStream_t st);

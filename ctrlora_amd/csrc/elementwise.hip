@@ -197,6 +197,50 @@ __global__ void qsample_kernel(const float* __restrict__ z, const float* __restr
     out[i] = a + b;
   }
 }
+// ---------------------------------------------------------------- q_sample + mask blend (cldm/ddim_hacked.py:154-157)
+// out = (sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * noise) * m + (1 - m) * x, m = mask[(per_b ? b : 0), (per_c ? c : 0), p]: the known
+// region of a masked sampling step re-noised to this step's time, the rest kept.  x0 / noise / x / out = [B][C][HW] fp32, t_b
+// clamped to [0, T - 1].  out may alias x (element-wise: every work item reads its own elements before it writes them), so
+// neither is __restrict__.  W = elements per work item (4: 16-byte loads and stores, 1: scalar); nw = B C HW / W work items.
+template <int W>
+__global__ void qsample_blend_kernel(const float* __restrict__ x0, const float* __restrict__ noise, const long* __restrict__ t,
+                                     const float* __restrict__ sqrt_ac, const float* __restrict__ sqrt_1mac, int T,
+                                     const float* __restrict__ mask, int per_b, int per_c, const float* x, float* out,
+                                     int C, long HW, long nw) {
+  // every torch op of q_sample(x0, t) * mask + (1. - mask) * img rounded once: two products and a sum (qsample_kernel), then a
+  // product, a difference, a product and a sum.  A contracted sum would differ from the eager loop in the last bit of some elements
+#pragma clang fp contract(off)
+  const long hw = HW / W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (long)gridDim.x * blockDim.x) {
+    const long bc = i / hw, j = (i - bc * hw) * W;
+    const long b = bc / C, c = bc - b * C;
+    long tb = t[b];
+    tb = tb < 0 ? 0 : (tb >= T ? T - 1 : tb);
+    const float sa = sqrt_ac[tb], s1 = sqrt_1mac[tb];
+    const long mrow = (per_b ? b : 0) * (per_c ? C : 1) + (per_c ? c : 0);
+    const long e = bc * HW + j, me = mrow * HW + j;
+    if constexpr (W == 4) {
+      const float4 z = *reinterpret_cast<const float4*>(x0 + e), n = *reinterpret_cast<const float4*>(noise + e);
+      const float4 m = *reinterpret_cast<const float4*>(mask + me), v = *reinterpret_cast<const float4*>(x + e);
+      float4 a, p, q, k, o;
+      a.x = sa * z.x; a.y = sa * z.y; a.z = sa * z.z; a.w = sa * z.w;
+      p.x = s1 * n.x; p.y = s1 * n.y; p.z = s1 * n.z; p.w = s1 * n.w;
+      q.x = a.x + p.x; q.y = a.y + p.y; q.z = a.z + p.z; q.w = a.w + p.w;
+      q.x = q.x * m.x; q.y = q.y * m.y; q.z = q.z * m.z; q.w = q.w * m.w;
+      k.x = 1.0f - m.x; k.y = 1.0f - m.y; k.z = 1.0f - m.z; k.w = 1.0f - m.w;
+      k.x = k.x * v.x; k.y = k.y * v.y; k.z = k.z * v.z; k.w = k.w * v.w;
+      o.x = q.x + k.x; o.y = q.y + k.y; o.z = q.z + k.z; o.w = q.w + k.w;
+      *reinterpret_cast<float4*>(out + e) = o;
+    } else {
+      const float a = sa * x0[e], p = s1 * noise[e];
+      const float q = a + p;
+      const float m = mask[me];
+      const float qm = q * m, k = 1.0f - m;
+      const float kx = k * x[e];
+      out[e] = qm + kx;
+    }
+  }
+}
 // ---------------------------------------------------------------- posterior sample (ddpm.py:655-662, distributions.py:35-37)
 // out = scale * (mean + std * e) for one or two tensors in ONE launch: mom = [B][2 per] (mean | std), e / out = [B][per], fp32.
 // work items [0, nw) belong to tensor a, [nw, 2 nw) to tensor b; W = elements per work item (4: 16-byte loads and stores, 1: scalar)
@@ -916,6 +960,29 @@ int qsample(const float* z, const float* noise, const long* t, const float* sqrt
   const dim3 grid(ew_grid(n));
   hipLaunchKernelGGL(qsample_kernel, grid, dim3(256), 0, st, z, noise, t, sqrt_ac, sqrt_1mac, out, per, n);
   return ew_done(EW_QSAMPLE, -1, grid, 256);
+}
+static inline bool overlaps(const float* a, long na, const float* b, long nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
+}
+int qsample_blend(const float* x0, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac, int T,
+                  const float* mask, int mask_per_batch, int mask_per_channel, const float* x, float* out, int B, int C, long HW,
+                  hipStream_t st) {
+  ew_rec_begin();
+  if (B < 0 || C < 1 || HW < 1 || T < 1) return CL_EINVAL;
+  if (B == 0) return CL_OK;
+  if (!x0 || !noise || !t || !sqrt_ac || !sqrt_1mac || !mask || !x || !out) return CL_EINVAL;
+  const int pb = mask_per_batch ? 1 : 0, pc = mask_per_channel ? 1 : 0;
+  const long n = (long)B * C * HW, nm = (long)(pb ? B : 1) * (pc ? C : 1) * HW;
+  // out is written while other work items still read x0 / noise / mask: only x may be out itself (the same element, in place)
+  if (overlaps(out, n, x0, n) || overlaps(out, n, noise, n) || overlaps(out, n, mask, nm)) return CL_EINVAL;
+  if (out != x && overlaps(out, n, x, n)) return CL_EINVAL;
+  const bool vec = HW % 4 == 0 && !mis16(x0) && !mis16(noise) && !mis16(mask) && !mis16(x) && !mis16(out);
+  const long nw = vec ? n / 4 : n;
+  const dim3 grid(ew_grid(nw));
+  if (vec) hipLaunchKernelGGL((qsample_blend_kernel<4>), grid, dim3(256), 0, st, x0, noise, t, sqrt_ac, sqrt_1mac, T, mask, pb, pc, x, out, C, HW, nw);
+  else hipLaunchKernelGGL((qsample_blend_kernel<1>), grid, dim3(256), 0, st, x0, noise, t, sqrt_ac, sqrt_1mac, T, mask, pb, pc, x, out, C, HW, nw);
+  return ew_done(EW_QSAMPLE_BLEND, -1, grid, 256, vec ? 1 : 0, pb | (pc << 1));
 }
 int posterior_sample_pair(const float* mom_a, const float* e_a, float* out_a, const float* mom_b, const float* e_b, float* out_b,
                           int B, long per, float scale, hipStream_t st) {

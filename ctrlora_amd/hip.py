@@ -125,6 +125,7 @@ _SIGS = {
     "cl_posterior_sample_pair": [_P, _P, _P, _P, _P, _P, _I, _L, _F, _P],
     "cl_plms_step": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "cl_plms_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
+    "cl_qsample_blend": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _L, _P],
 }
 EXPORTED = tuple(_SIGS.keys())
 # probe hooks (ctrlora_amd/csrc/debug_hooks.h): exported by the library, not part of include/ctrlora_hip.h
@@ -713,6 +714,28 @@ def qsample(z, noise, t, sqrt_ac, sqrt_1mac, out):
     B = z.shape[0]
     _chk(lib().cl_qsample(z.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
                           out.data_ptr(), B, z.numel() // B, stream()), "cl_qsample")
+    return out
+
+
+def qsample_blend(x0, noise, t, sqrt_ac, sqrt_1mac, mask, x, out):
+    """out = q_sample(x0, t) * mask + (1 - mask) * x in one launch (cl_qsample_blend): x0 / noise / x / out [B, C, H, W], mask
+    [B | 1, C | 1, H, W], t [B] long, the tables [T]; fp32 except t, contiguous.  out may be x.  Bit-identical to qsample()
+    followed by the three torch fp32 ops."""
+    B, Cn = x0.shape[0], x0.shape[1]
+    hw = tuple(x0.shape[2:])
+    if mask.dim() != x0.dim() or tuple(mask.shape[2:]) != hw or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cn):
+        raise ValueError(f"mask {tuple(mask.shape)} is none of the layouts (B | 1, C | 1, H, W) of a sample {tuple(x0.shape)}")
+    for v in (x0, noise, sqrt_ac, sqrt_1mac, mask, x, out):
+        assert v.dtype == torch.float32 and v.is_contiguous()
+    assert t.dtype == torch.long and t.is_contiguous() and t.numel() == B
+    assert noise.shape == x0.shape == x.shape == out.shape and sqrt_ac.numel() == sqrt_1mac.numel()
+    HW = 1
+    for d in hw:
+        HW *= int(d)
+    # a dimension of size 1 is broadcast (with B == 1 or C == 1 both readings address the same plane)
+    _chk(lib().cl_qsample_blend(x0.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
+                                sqrt_ac.numel(), mask.data_ptr(), int(mask.shape[0] != 1), int(mask.shape[1] != 1),
+                                x.data_ptr(), out.data_ptr(), B, Cn, HW, stream()), "cl_qsample_blend")
     return out
 
 

@@ -415,12 +415,26 @@ int cl_conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, 
 int cl_softmax_rows(int dtype, const float* S, long lds, void* P, long ldp, long M, int N, float scale, void* stream);
 
 /* ---- diffusion bookkeeping ------------------------------------------------------------ */
-/* Refusals of the entry points below, besides null required pointers (optional: d_eps, e_u, noise, pred_x0, lvlb, per_sample): a
+/* Forward process (q_sample, alone or blended into a masked sampling step), the first-stage posterior sample, the losses, the
+ * fused sampler updates and the optimizer step.
+ * Refusals of the entry points below, besides null required pointers (optional: d_eps, e_u, noise, pred_x0, lvlb, per_sample): a
  * negative n / B / per_sample; cl_p_losses_mse B outside 1 .. 65535, per_sample_elems < 1, lvlb without t; cl_ddim_step index < 0;
- * cl_adamw_dev needs hyper and step even when n == 0.  cl_zero(p, 0) is CL_OK. */
+ * cl_adamw_dev needs hyper and step even when n == 0.  cl_zero(p, 0) is CL_OK.  cl_qsample_blend lists its own. */
 /* DDPM.q_sample (ddpm.py:356-359): out = sqrt_ac[t_b] * z + sqrt_1mac[t_b] * noise */
 int cl_qsample(const float* z, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
                float* out, int B, long per_sample, void* stream);
+/* One masked sampling step's blend (cldm/ddim_hacked.py:154-157 with ddpm.py q_sample), added in ABI 7 (compatible):
+ *   out[b, c, p] = (sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * noise) * m + (1 - m) * x,  m = mask[(mask_per_batch ? b : 0),
+ *   (mask_per_channel ? c : 0), p] -- the four mask layouts (B | 1, C | 1, H, W); x0 / noise / x / out = [B][C][HW] fp32; t_b is
+ * clamped to [0, T - 1] (the tables hold T entries).  Every torch fp32 op rounded once, no FMA: q = rn(rn(sa x0) + rn(s1 noise)),
+ * out = rn(rn(q m) + rn(rn(1 - m) x)) -- the bits of cl_qsample followed by the three torch ops.  out may be x (in place).
+ * 16-byte loads and stores where HW % 4 == 0 and x0 / noise / mask / x / out are 16-byte aligned, scalar otherwise.  No host
+ * synchronisation, no allocation; the time comes from device memory, so a captured launch replays unchanged.
+ * Refused: B < 0, C < 1, HW < 1, T < 1; with B > 0 a null pointer, out overlapping x0 / noise / mask, out overlapping x without
+ * being x.  B == 0 is CL_OK. */
+int cl_qsample_blend(const float* x0, const float* noise, const long* t, const float* sqrt_ac, const float* sqrt_1mac,
+                     int T, const float* mask, int mask_per_batch, int mask_per_channel, const float* x, float* out,
+                     int B, int C, long HW, void* stream);
 /* LatentDiffusion.get_first_stage_encoding on a stored posterior (ddpm.py:655-662, distributions.py:35-37), added in ABI 7
  * (compatible): out = scale * (mean + std * e), fp32, for one tensor or for two of the same shape in ONE launch (target and
  * condition of a training batch).  mom_* = [B][2 per_sample] (mean, then std, of each sample); e_* and out_* = [B][per_sample].

@@ -39,6 +39,9 @@ def get_parser():
                    help="ddim (the reference script's sampler); dpm: DPM-Solver++ (multistep, order 2), which takes "
                         "--ddim_steps as its number of steps (20 is usual) and ignores --ddim_eta; or plms: the pseudo "
                         "linear multistep sampler on DDIM's schedule, which needs --ddim_eta 0")
+    p.add_argument("--init_strength", type=float, default=1.0,
+                   help="below 1: img2img from the dataset's target image -- it is noised to step int(init_strength * ddim_steps) "
+                        "of the schedule and the remaining steps run from there (--sampler ddim only); 1.0: sample from noise")
     return p
 
 
@@ -73,8 +76,14 @@ def sample_dataset(model, sampler, dataset, args, device="cuda"):
             cond = {"c_concat": [control], "c_crossattn": [model.get_learned_conditioning([prompt])], "task": args.task}
             un_cond = {"c_concat": [control], "c_crossattn": [model.get_learned_conditioning([""])], "task": args.task}
             model.control_scales = [args.strength] * 13
-            samples, _ = sampler.sample(args.ddim_steps, 1, (4, H // 8, W // 8), cond, verbose=False, eta=args.ddim_eta,
-                                        unconditional_guidance_scale=args.cfg, unconditional_conditioning=un_cond)
+            if getattr(args, "init_strength", 1.0) < 1.0:
+                import api
+                api.check_edit_args(img, args.init_strength, None)
+                samples = api.img2img_latents(sampler, api.encode_init(model, img, 1), cond, un_cond, args.ddim_steps,
+                                              args.init_strength, args.cfg, eta=args.ddim_eta)
+            else:
+                samples, _ = sampler.sample(args.ddim_steps, 1, (4, H // 8, W // 8), cond, verbose=False, eta=args.ddim_eta,
+                                            unconditional_guidance_scale=args.cfg, unconditional_conditioning=un_cond)
             x = model.decode_first_stage(samples)[0]
             x = (x.permute(1, 2, 0) * 127.5 + 127.5).cpu().numpy().clip(0, 255).astype(np.uint8)
             Image.fromarray(x).save(os.path.join(args.save_dir, "sample", f"{idx}.png"))
@@ -102,6 +111,8 @@ def main(argv=None):
     from cldm.cldm_ctrlora_pretrain import ControlPretrainLDM
     from cldm.model import create_model, load_state_dict
     args = get_parser().parse_args(argv)
+    if args.init_strength != 1.0 and args.sampler != "ddim":
+        raise SystemExit("--init_strength needs --sampler ddim (the other samplers have no decode())")
     if args.multigen20m:
         from datasets.multigen20m import MultiGen20M
         dataset = MultiGen20M(path_json=os.path.join(args.dataroot, "json_files", f"aesthetics_plus_all_group_{args.task}_all.json"),
