@@ -30,17 +30,18 @@ class ControlNetPretrain(ControlNet):
         self._lora_names = [ids[id(m)] for m in self._lora_linears]
         self._task = None
 
-    def switch_lora(self, task: str):
-        """:68-76 -- point every LoRACompatibleLinear at the task's bank.  The executor is kept (an optimizer may hold
-        its flat buffers): the engine swaps the active LoRA bank and re-packs only the LoRA factors."""
+    def switch_lora(self, task: str, repacked: bool = False):
+        """:68-76 -- point every LoRACompatibleLinear at the task's bank.  The executor is kept (an optimizer may hold its flat
+        buffers): the engine swaps the active LoRA bank and re-packs only the LoRA factors -- or, repacked=True, moves only
+        the host-side pointers after a replayed hipGraph has re-packed that bank on the device."""
         assert task in self.tasks
         for lin, lora in zip(self._lora_linears, self.loras_dict[task]):
             lin.set_lora_layer(lora)
-        if task != self._task:
+        if task != self._task or repacked:
             self._task = task
             ex = self.__dict__.get("_exec")
             if ex is not None:
-                ex.switch_bank(self.bank(task))
+                ex.switch_bank(self.bank(task), repack=not repacked)
 
     def _executor_state(self):
         return {k: v for k, v in self.state_dict().items() if not k.startswith("loras_dict.")}

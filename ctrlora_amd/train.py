@@ -7,11 +7,14 @@
                       (ddpm.py:902-918 with logvar = 0).
   * FusedAdamW     -- torch.optim.AdamW semantics (cldm_ctrlora_finetune.py:105) as ONE kernel over the
                       flat master/grad buffers, followed by the re-pack of the trainables.
+  * PretrainAdamW  -- the same over the base buffer and every LoRA bank that has joined (both: _FlatAdamW + _AdamState).
   * bind_trainables -- re-points the ControlNet's trainable nn.Parameters at the flat buffers.
+  * GraphedTrainStep -- the optimizer step as hipGraph replays of the pieces capture_plan() lists.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from functools import partial
+from typing import List, NamedTuple, Sequence
 
 import torch
 
@@ -86,31 +89,105 @@ class PLossFn(torch.autograd.Function):
         return d_eps * g[2], None, None, None, None, None
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """AdamW over the engine's flat buffers.  `params` are the bound nn.Parameters (kept in param_groups
-    for scheduler / checkpoint compatibility); the arithmetic is one HIP kernel per ControlNet bank.
+class _AdamState:
+    """The Adam state of ONE TrainableSet: the flat moments `m`, `v` (in the order of `ts.flat`) and a device step counter --
+    its own, or one handed in that several states share.  `legacy(src)` is the owning optimizer's rule for a moment saved as
+    one flat tensor: it returns the [(offset here, offset in src, numel)] to copy, or raises."""
 
-    Step count and hyper-parameters live in DEVICE memory (cl_adamw_dev), so that `step()` can be captured
-    in a hipGraph and replayed: a learning-rate schedule only has to refresh the 6-float `hyper` tensor
-    (`sync_hyper()`, done automatically outside capture)."""
+    def __init__(self, ts, step=None, legacy=None):
+        self.ts, self.legacy = ts, legacy
+        self.m, self.v = torch.zeros_like(ts.flat), torch.zeros_like(ts.flat)
+        self.step = torch.zeros(1, dtype=torch.int32, device=ts.flat.device) if step is None else step
 
-    def __init__(self, params, executors, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 grad_scale: float = 1.0):
+    def __getitem__(self, key):          # state["m" | "v" | "step"]
+        return getattr(self, key)
+
+    def _by_name(self, buf):
+        return ((t.name, buf[t.offset:t.offset + t.master.numel()]) for t in self.ts.items)
+
+    def export(self):
+        """Moments BY PARAMETER NAME: the order of the flat buffers is an implementation detail of a build / dtype (the bf16
+        engine keeps the grouped emb_layers factors at the tail, nets.py), a checkpoint must not depend on it."""
+        return dict(m={n: x.clone() for n, x in self._by_name(self.m)}, v={n: x.clone() for n, x in self._by_name(self.v)},
+                    step=int(self.step.item()))
+
+    def check(self, src, allow_surplus):
+        """Raise if `src` = {m, v, step} cannot be loaded; nothing is written."""
+        int(src["step"])
+        for key in ("m", "v"):
+            if not isinstance(src[key], dict):
+                self.legacy(src[key])
+                continue
+            missing = [t.name for t in self.ts.items if t.name not in src[key]]
+            if missing:
+                raise KeyError(f"optimizer state lacks {len(missing)} tensors, e.g. {missing[:3]}")
+            surplus = [] if allow_surplus else sorted(set(src[key]) - set(self.ts.by_name))
+            if surplus:
+                raise KeyError(f"optimizer state holds {len(surplus)} tensors this model does not train, "
+                               f"e.g. {surplus[:3]} (norm_trainable / zero_trainable differ from the checkpoint's?)")
+
+    def load(self, src):
+        """Copy a checked `src` in."""
+        for key in ("m", "v"):
+            dst, saved = self[key], src[key]
+            if isinstance(saved, dict):
+                for name, x in self._by_name(dst):
+                    x.copy_(saved[name].reshape(-1))
+            else:
+                saved = saved.reshape(-1)
+                for here, there, k in self.legacy(saved):
+                    dst[here:here + k].copy_(saved[there:there + k])
+        self.step.fill_(int(src["step"]))
+
+
+def _load_states(pairs):
+    """[(state, src, allow_surplus)]: every check before the first copy, so a refused state dict leaves the optimizer -- step
+    counters included -- as it was (e.g. a resume under other norm_trainable / zero_trainable flags)."""
+    for st, src, allow_surplus in pairs:
+        st.check(src, allow_surplus)
+    for st, src, _ in pairs:
+        st.load(src)
+
+
+def _legacy_rounds_1_3(ex, src):
+    """FusedAdamW: a flat moment tensor saved by rounds 1-3.  Those builds laid the trainables out in `ex.legacy_item_names`
+    order (backward-completion order without the emb_layers hoist), every tensor padded to 64 floats
+    (packing.TrainableSet.materialize); the tensors are found by walking that order and go to today's offsets."""
+    from .engine.packing import rup
+    names = getattr(ex, "legacy_item_names", None) or [t.name for t in ex.tr.items]
+    by_name = {t.name: t for t in ex.tr.items}
+    if sorted(names) != sorted(by_name):
+        raise KeyError("the legacy optimizer state does not describe this model's trainable set")
+    off, spans = 0, []
+    for n in names:
+        k = by_name[n].master.numel()
+        spans.append((by_name[n].offset, off, k))
+        off += rup(k, 64)
+    if off != src.numel():
+        raise ValueError(f"legacy optimizer state holds {src.numel()} floats, the legacy layout of this model has {off}")
+    return spans
+
+
+def _legacy_format_1(ts, src):
+    """PretrainAdamW format 1 (rounds 2-4): the raw flat buffer; only valid for an unchanged layout -- check what can be."""
+    if src.numel() != ts.flat.numel():
+        raise ValueError(f"flat optimizer state of {src.numel()} floats does not fit this build's {ts.flat.numel()}")
+    return [(0, 0, src.numel())]
+
+
+class _FlatAdamW(torch.optim.Optimizer):
+    """What the two optimizers over the engine's flat buffers share; a subclass launches its kernels in `_update()` and
+    `zero_grad()`.  `params` are the bound nn.Parameters (kept in param_groups for scheduler / checkpoint compatibility); step
+    counts and hyper-parameters live in DEVICE memory (cl_adamw_dev), so that `step()` can be captured in a hipGraph and
+    replayed: a schedule only has to refresh the 6-float `hyper` tensor (`sync_hyper()`, automatic outside capture)."""
+
+    def __init__(self, params, device, lr, betas, eps, weight_decay, grad_scale):
         super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.executors = list(executors)
         self.grad_scale = grad_scale
-        dev = self.executors[0].tr.flat.device
-        self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._hyper = torch.zeros(6, dtype=torch.float32, device=dev)
+        self._hyper = torch.zeros(6, dtype=torch.float32, device=device)
         self._hyper_host = None
-        self._m = [torch.zeros_like(ex.tr.flat) for ex in self.executors]
-        self._v = [torch.zeros_like(ex.tr.flat) for ex in self.executors]
         self.pre_step_hook = None     # e.g. DP: wait for the gradient all-reduce
         self.sync_hyper()
-
-    @property
-    def _step(self) -> int:
-        return int(self._step_dev.item())
 
     def sync_hyper(self):
         """Push {lr, betas, eps, weight_decay, grad_scale} to the device if they changed (host -> device copy:
@@ -127,13 +204,43 @@ class FusedAdamW(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         if self.pre_step_hook is not None:
             self.pre_step_hook()
-        if not torch.cuda.is_current_stream_capturing():
+        if not torch.cuda.is_available() or not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
-        hip.tick(self._step_dev)          # one tick per optimizer step, however many banks follow
-        for ex, m, v in zip(self.executors, self._m, self._v):
-            hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, m, v, self._hyper, self._step_dev)
-            ex.repack()
+        self._update()
         return loss
+
+    def _saved_param_groups(self):
+        return [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+
+    def _restore_param_groups(self, sd):
+        """Resume: the saved hyper-parameters (a scheduler may have moved lr) replace the constructor's, then go to the device."""
+        for g, saved in zip(self.param_groups, sd.get("param_groups") or []):
+            for k, v in saved.items():
+                if k != "params":
+                    g[k] = v
+        self.sync_hyper()
+
+
+class FusedAdamW(_FlatAdamW):
+    """AdamW over the engine's flat buffers for fine-tuning: one HIP kernel per ControlNet bank, all banks on ONE step
+    counter, each followed by the re-pack of its trainables."""
+
+    def __init__(self, params, executors, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale: float = 1.0):
+        self.executors = list(executors)
+        dev = self.executors[0].tr.flat.device
+        super().__init__(params, dev, lr, betas, eps, weight_decay, grad_scale)
+        self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._states = [_AdamState(ex.tr, self._step_dev, partial(_legacy_rounds_1_3, ex)) for ex in self.executors]
+
+    _step = property(lambda self: int(self._step_dev.item()))
+    _m = property(lambda self: [st.m for st in self._states])
+    _v = property(lambda self: [st.v for st in self._states])
+
+    def _update(self):
+        hip.tick(self._step_dev)          # one tick per optimizer step, however many banks follow
+        for ex, st in zip(self.executors, self._states):
+            hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
+            ex.repack()
 
     def zero_grad(self, set_to_none: bool = False):
         # .grad tensors are views of flat_grad: zero in place, they must stay attached
@@ -141,72 +248,17 @@ class FusedAdamW(torch.optim.Optimizer):
             hip.zero_(ex.tr.flat_grad)
 
     def state_dict(self):
-        """Moments BY PARAMETER NAME: the order of the flat buffers is an implementation detail of a build / dtype (the bf16
-        engine keeps the grouped emb_layers factors at the tail, nets.py), a checkpoint must not depend on it."""
-        def by_name(ex, buf):
-            return {t.name: buf[t.offset:t.offset + t.master.numel()].clone() for t in ex.tr.items}
-        return dict(step=self._step, format="by_name", m=[by_name(ex, m) for ex, m in zip(self.executors, self._m)],
-                    v=[by_name(ex, v) for ex, v in zip(self.executors, self._v)],
-                    param_groups=[{k: v for k, v in g.items() if k != "params"} for g in self.param_groups])
+        saved = [st.export() for st in self._states]
+        return dict(step=self._step, format="by_name", m=[s["m"] for s in saved], v=[s["v"] for s in saved],
+                    param_groups=self._saved_param_groups())
 
     def load_state_dict(self, sd):
-        assert len(sd["m"]) == len(self._m), "optimizer state was saved for a different number of ControlNet banks"
-        # every check first: a refused state (e.g. a resume under other norm_trainable / zero_trainable flags) leaves this
-        # optimizer -- step counter included -- as it was
-        for key in ("m", "v"):
-            for ex, src in zip(self.executors, sd[key]):
-                if not isinstance(src, dict):
-                    continue
-                missing = [t.name for t in ex.tr.items if t.name not in src]
-                if missing:
-                    raise KeyError(f"optimizer state lacks {len(missing)} tensors, e.g. {missing[:3]}")
-                surplus = sorted(set(src) - set(ex.tr.by_name))
-                if surplus:
-                    raise KeyError(f"optimizer state holds {len(surplus)} tensors this model does not train, "
-                                   f"e.g. {surplus[:3]} (norm_trainable / zero_trainable differ from the checkpoint's?)")
-        for key, bufs in (("m", self._m), ("v", self._v)):
-            for ex, dst, src in zip(self.executors, bufs, sd[key]):
-                if isinstance(src, dict):
-                    for t in ex.tr.items:
-                        dst[t.offset:t.offset + t.master.numel()].copy_(src[t.name].reshape(-1))
-                else:       # rounds 1-3: ONE flat tensor in the flat buffer's order of the build that wrote it (no emb hoist)
-                    _load_legacy_flat(ex, dst, src)
-        self._step_dev.fill_(int(sd["step"]))
-        _restore_param_groups(self, sd)
+        assert len(sd["m"]) == len(self._states), "optimizer state was saved for a different number of ControlNet banks"
+        _load_states([(st, dict(m=m, v=v, step=sd["step"]), False) for st, m, v in zip(self._states, sd["m"], sd["v"])])
+        self._restore_param_groups(sd)
 
 
-def _load_legacy_flat(ex, dst, src):
-    """A flat moment tensor saved by rounds 1-3 -> this build's layout.  Those builds laid the trainables out in
-    `ex.legacy_item_names` order (backward-completion order without the emb_layers hoist), every tensor padded to 64 floats
-    (packing.TrainableSet.materialize); the tensors are found by walking that order and copied to today's offsets."""
-    from .engine.packing import rup
-    names = getattr(ex, "legacy_item_names", None) or [t.name for t in ex.tr.items]
-    by_name = {t.name: t for t in ex.tr.items}
-    if sorted(names) != sorted(by_name):
-        raise KeyError("the legacy optimizer state does not describe this model's trainable set")
-    off = 0
-    spans = []
-    for n in names:
-        k = by_name[n].master.numel()
-        spans.append((by_name[n], off, k))
-        off += rup(k, 64)
-    if off != src.numel():
-        raise ValueError(f"legacy optimizer state holds {src.numel()} floats, the legacy layout of this model has {off}")
-    src = src.reshape(-1)
-    for t, o, k in spans:
-        dst[t.offset:t.offset + k].copy_(src[o:o + k])
-
-
-def _restore_param_groups(opt, sd):
-    """Resume: the saved hyper-parameters (a scheduler may have moved lr) replace the constructor's, then go to the device."""
-    for g, saved in zip(opt.param_groups, sd.get("param_groups") or []):
-        for k, v in saved.items():
-            if k != "params":
-                g[k] = v
-    opt.sync_hyper()
-
-
-class PretrainAdamW(torch.optim.Optimizer):
+class PretrainAdamW(_FlatAdamW):
     """torch.optim.AdamW over ALL ControlNet parameters as the reference's multi-task pre-training uses it
     (cldm/cldm_ctrlora_pretrain.py:174-182, torch 1.13 / Lightning 1.5 semantics), on the engine's flat buffers:
 
@@ -219,53 +271,24 @@ class PretrainAdamW(torch.optim.Optimizer):
     `mark_used(task)` is called by the model when a task's bank took part in a backward pass."""
 
     def __init__(self, params, executor, banks, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
-        super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.executor, self.banks = executor, dict(banks)
-        self.executors = [executor]
-        self.grad_scale = grad_scale
-        dev = executor.tr.flat.device
-        self._hyper = torch.zeros(6, dtype=torch.float32, device=dev)
-        self._hyper_host = None
-        mk = lambda ts: dict(m=torch.zeros_like(ts.flat), v=torch.zeros_like(ts.flat),
-                             step=torch.zeros(1, dtype=torch.int32, device=dev))
+        self.executor, self.executors, self.banks = executor, [executor], dict(banks)
+        super().__init__(params, executor.tr.flat.device, lr, betas, eps, weight_decay, grad_scale)
+        mk = lambda ts: _AdamState(ts, legacy=partial(_legacy_format_1, ts))
         self._base = mk(executor.tr)
         self._bank_state = {k: mk(ts) for k, ts in self.banks.items()}
         self.active = []                 # tasks whose bank has received a gradient at least once, in order of first use
-        self.pre_step_hook = None
-        self.sync_hyper()
-
-    def sync_hyper(self):
-        g = self.param_groups[0]
-        cur = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-               float(self.grad_scale))
-        if cur != self._hyper_host:
-            self._hyper.copy_(torch.tensor(cur, dtype=torch.float32))
-            self._hyper_host = cur
 
     def mark_used(self, task):
         if task not in self.active:
             self.active.append(task)
 
-    @property
-    def _step(self) -> int:
-        return int(self._base["step"].item())
+    _step = property(lambda self: int(self._base.step.item()))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        if self.pre_step_hook is not None:
-            self.pre_step_hook()
-        if not torch.cuda.is_available() or not torch.cuda.is_current_stream_capturing():
-            self.sync_hyper()
-        ex = self.executor
-        hip.tick(self._base["step"])
-        hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, self._base["m"], self._base["v"], self._hyper, self._base["step"])
-        for task in self.active:
-            ts, st = self.banks[task], self._bank_state[task]
-            hip.tick(st["step"])
-            hip.adamw_dev(ts.flat, ts.flat_grad, st["m"], st["v"], self._hyper, st["step"])
-        ex.repack()
-        return loss
+    def _update(self):
+        for ts, st in [(self.executor.tr, self._base)] + [(self.banks[k], self._bank_state[k]) for k in self.active]:
+            hip.tick(st.step)
+            hip.adamw_dev(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step)
+        self.executor.repack()
 
     def zero_grad(self, set_to_none: bool = False):
         hip.zero_(self.executor.tr.flat_grad)
@@ -273,35 +296,50 @@ class PretrainAdamW(torch.optim.Optimizer):
             hip.zero_(self.banks[task].flat_grad)
 
     def state_dict(self):
-        """Moments BY PARAMETER NAME (format 2), like FusedAdamW: the flat buffers' order is a detail of a build."""
-        def pack(ts, st):
-            by = lambda buf: {t.name: buf[t.offset:t.offset + t.master.numel()].clone() for t in ts.items}
-            return dict(m=by(st["m"]), v=by(st["v"]), step=int(st["step"].item()))
-        return dict(format="by_name", version=2, base=pack(self.executor.tr, self._base),
-                    banks={k: pack(self.banks[k], v) for k, v in self._bank_state.items()}, active=list(self.active),
-                    param_groups=[{k: v for k, v in g.items() if k != "params"} for g in self.param_groups])
+        """Format 2: moments by parameter name, like FusedAdamW."""
+        return dict(format="by_name", version=2, base=self._base.export(),
+                    banks={k: st.export() for k, st in self._bank_state.items()}, active=list(self.active),
+                    param_groups=self._saved_param_groups())
 
     def load_state_dict(self, sd):
-        def unpack(ts, st, src):
-            for key in ("m", "v"):
-                if isinstance(src[key], dict):
-                    missing = [t.name for t in ts.items if t.name not in src[key]]
-                    if missing:
-                        raise KeyError(f"optimizer state lacks {len(missing)} tensors, e.g. {missing[:3]}")
-                    for t in ts.items:
-                        st[key][t.offset:t.offset + t.master.numel()].copy_(src[key][t.name].reshape(-1))
-                else:       # format 1 (rounds 2-4): raw flat buffers; only valid for an unchanged layout -- check what can be checked
-                    if src[key].numel() != st[key].numel():
-                        raise ValueError(f"flat optimizer state of {src[key].numel()} floats does not fit this build's {st[key].numel()}")
-                    st[key].copy_(src[key])
-            st["step"].fill_(int(src["step"]))
         if set(sd["banks"]) != set(self._bank_state):
             raise KeyError(f"optimizer state holds banks {sorted(sd['banks'])}, the model has {sorted(self._bank_state)}")
-        unpack(self.executor.tr, self._base, sd["base"])
-        for k, src in sd["banks"].items():
-            unpack(self.banks[k], self._bank_state[k], src)
-        self.active = list(sd["active"])
-        _restore_param_groups(self, sd)
+        active = list(sd["active"])
+        _load_states([(self._base, sd["base"], True)] + [(self._bank_state[k], src, True) for k, src in sd["banks"].items()])
+        self.active = active
+        self._restore_param_groups(sd)
+
+
+class Piece(NamedTuple):
+    """One captured piece of an optimizer step (capture_plan)."""
+    kind: str                 # "Z" = zero_grad, "F" = forward + loss + backward, "B" = opt.step()
+    segmented: bool = False   # F: the stage-cut segment graphs instead of one graph
+    tag: object = None        # F: what is exchanged after it -- None, "all", or "per-segment" (int tags, then "tails")
+    zero: bool = False        # F: clears the gradients itself
+    with_opt: bool = False    # F: opt.step() is captured inside the same graph (there is no B)
+
+
+def capture_plan(mode: str, accumulate: bool) -> List[Piece]:
+    """The pieces of one GraphedTrainStep in capture and replay order, always [Z] F [B]: Z iff `accumulate` (else F clears
+    the gradients itself), B as a graph of its own except in ("one", no accumulation), where opt.step() closes F's graph."""
+    tag = {"one": None, "two": "all", "segmented": "per-segment"}[mode]
+    fused = mode == "one" and not accumulate
+    f = Piece("F", segmented=mode == "segmented", tag=tag, zero=not accumulate, with_opt=fused)
+    return ([Piece("Z")] if accumulate else []) + [f] + ([] if fused else [Piece("B")])
+
+
+class _StaticInputs:
+    """The five tensors (z, ctx, hint, t, noise) a captured step reads: clones made once, refilled before every replay."""
+
+    def __init__(self, *tensors):
+        self.tensors = tuple(x.clone() for x in tensors)
+
+    def load(self, *tensors):
+        for dst, src in zip(self.tensors, tensors):
+            dst.copy_(src)
+
+    def matches(self, *tensors) -> bool:
+        return all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(tensors, self.tensors))
 
 
 class GraphedTrainStep:
@@ -329,18 +367,11 @@ class GraphedTrainStep:
     `model` is a ControlFinetuneLDM-like module (engine_train_step or p_losses / dp / control_model), `opt` its
     FusedAdamW.
 
-    A training loop (ctrlora_amd.trainer.Trainer) must not spend batches on warm-up, and under gradient accumulation one
-    optimizer step is several forward + backward passes.  For that:
-
-      * `warmup=0, capture=False` builds the object without running or capturing anything; `eager(...)` then runs one
-        micro-step with ordinary launches on the same direct path (each on its own batch), and `capture()` records the
-        graphs once the allocations are warm.
-      * `accumulate=True` captures the step as three pieces in every mode -- Z = zero_grad, F = forward + backward ADDING to
-        the gradient buffer (one graph, or the segments), B = AdamW + re-pack -- and `micro(..., first=, last=)` replays
-        [Z] F [B]: the first micro-step of an optimizer step clears, only the last one exchanges and optimizes.
-      * `grad_scale` multiplies d loss / d eps in every pass (1 / accumulate_grad_batches); it is a by-value kernel
-        argument, constant for a run, so it is baked into the capture.
-    """
+    For a training loop (ctrlora_amd.trainer.Trainer): `warmup=0, capture=False` builds the object without
+    running or capturing anything, `eager(...)` runs one micro-step with ordinary launches on the same direct path, and
+    `capture()` records the graphs once the allocations are warm.  `accumulate=True` captures the step as three pieces in
+    every mode (capture_plan) and `micro(..., first=, last=)` replays [Z] F [B].  `grad_scale` multiplies d loss / d eps in
+    every pass (1 / accumulate_grad_batches); a by-value kernel argument, constant for a run, so baked into the capture."""
 
     def __init__(self, model, opt, z, cond_txt, hint, t, noise, warmup: int = 2, split_graphs=None,
                  bucket_bytes: int = 32 << 20, reduce_fn=None, capture_error_mode=None, grad_scale: float = 1.0,
@@ -351,23 +382,13 @@ class GraphedTrainStep:
         # With a process group alive, RCCL's watchdog thread polls events while this thread captures: only calls made
         # by the capturing thread may invalidate the capture ("thread_local"); single-process keeps the strict default.
         self.capture_error_mode = capture_error_mode or ("thread_local" if self.world > 1 else "global")
-        self.dist = dist
         if split_graphs is None:
-            mode = "segmented" if self.world > 1 else "one"
-        elif split_graphs in ("segmented", True):
-            mode = "segmented"
-        elif split_graphs == "two":
-            mode = "two"
-        else:
-            mode = "one"
-        self.mode = mode
-        self.s_z, self.s_ctx, self.s_hint = z.clone(), cond_txt.clone(), hint.clone()
-        self.s_t, self.s_noise = t.clone(), noise.clone()
-        self.loss = None
-        self.loss3 = None
-        dp = model.dp
-        if dp is not None:
-            dp.enabled = False          # no collectives inside the captured regions: this class issues them itself
+            split_graphs = self.world > 1
+        self.mode = mode = {True: "segmented", "segmented": "segmented", "two": "two"}.get(split_graphs, "one")
+        self._static = _StaticInputs(z, cond_txt, hint, t, noise)
+        self.loss = self.loss3 = None
+        if model.dp is not None:
+            model.dp.enabled = False    # no collectives inside the captured regions: this class issues them itself
         # reduce_fn(tensor_slice) -> work handle with .wait() or None; default: RCCL SUM all-reduce, asynchronous
         if reduce_fn is None:
             from .parallel import all_reduce_slice, payload_dtype_from_env
@@ -378,28 +399,21 @@ class GraphedTrainStep:
                     return all_reduce_slice(buf, None, payload)
                 return None
         self._reduce_fn = reduce_fn
-
-        self.grad_scale, self.accumulate = float(grad_scale), bool(accumulate)
-        self.bucket_bytes = bucket_bytes
-        self._static = (self.s_z, self.s_ctx, self.s_hint, self.s_t, self.s_noise)
-
-        hook, opt.pre_step_hook = opt.pre_step_hook, None
-        self._hook = hook
+        self.grad_scale, self.accumulate, self.bucket_bytes = float(grad_scale), bool(accumulate), bucket_bytes
+        opt.pre_step_hook = None          # the exchange it would wait for is issued by this class
         self._side = side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                self._fwd_bwd(self._static)
+                self._fwd_bwd(self._static.tensors)
                 if mode != "one":
                     self._reduce_all()
                 opt.step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.segments = []               # [(graph, executor index or None, lo, hi)]
-        self.g_b = None
-        self.g_z = None                  # accumulate=True: zero_grad as a piece of its own
-        self.captured = False
-        self.warmup_steps = warmup
+        self.g_z = self.g_b = None       # the Z and B pieces, where capture_plan has them
+        self.captured, self.warmup_steps = False, warmup
         if capture:
             self.capture()
 
@@ -447,58 +461,39 @@ class GraphedTrainStep:
     def capture(self):
         """Record the graphs on the static tensors.  Capturing executes nothing."""
         assert not self.captured, "captured already"
-        opt, mode = self.opt, self.mode
-
-        def fwd_bwd():
-            loss, self.loss3 = self._fwd_bwd(self._static, zero=not self.accumulate)
-            return loss
+        opt = self.opt
         torch.cuda.synchronize()
         opt.sync_hyper()
-        if self.accumulate:
-            self.g_z = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_z, capture_error_mode=self.capture_error_mode):
-                opt.zero_grad()
-            if mode == "segmented":
-                self._capture_segments(fwd_bwd, max(1, self.bucket_bytes // 4))
-                pool = self._pool
+        self._pool = torch.cuda.graph_pool_handle()      # every piece of this step object allocates from one pool
+        for piece in capture_plan(self.mode, self.accumulate):
+            if piece.kind == "Z":
+                self.g_z = self._capture(opt.zero_grad)
+            elif piece.kind == "B":
+                self.g_b = self._capture(opt.step)
             else:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.g_z.pool(), capture_error_mode=self.capture_error_mode):
-                    self.loss = fwd_bwd()
-                self.segments.append((g, "all" if mode == "two" else None, 0, 0))
-                pool = self.g_z.pool()
-            self.g_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_b, pool=pool, capture_error_mode=self.capture_error_mode):
-                opt.step()
-        elif mode == "one":
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
-                self.loss = fwd_bwd()
-                opt.step()
-            self.segments.append((g, None, 0, 0))
-        elif mode == "two":
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=self.capture_error_mode):
-                self.loss = fwd_bwd()
-            self.segments.append((g, "all", 0, 0))
-            self.g_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_b, pool=g.pool(), capture_error_mode=self.capture_error_mode):
-                opt.step()
-        else:
-            self._capture_segments(fwd_bwd, max(1, self.bucket_bytes // 4))
-            self.g_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_b, pool=self._pool, capture_error_mode=self.capture_error_mode):
-                opt.step()
+                def fwd_bwd():
+                    self.loss, self.loss3 = self._fwd_bwd(self._static.tensors, zero=piece.zero)
+                    if piece.with_opt:
+                        opt.step()
+                if piece.segmented:
+                    self._capture_segments(fwd_bwd, max(1, self.bucket_bytes // 4))
+                else:
+                    self.segments.append((self._capture(fwd_bwd), piece.tag, 0, 0))
         self.captured = True
+
+    def _capture(self, fn):
+        """Record what `fn` launches as a new graph in this step object's pool."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._pool, capture_error_mode=self.capture_error_mode):
+            fn()
+        return g
 
     def _capture_segments(self, fwd_bwd, bucket_elems):
         """Capture forward + backward as consecutive graphs that end where a gradient bucket is complete.  The
         executors' stage-completion hook (ControlNetE._done -> on_stage_done(start, end), called after the stage's last
         kernel was enqueued) closes the running capture and opens the next one in the same memory pool."""
-        opt = self.opt
-        execs = list(opt.executors)
+        execs = list(self.opt.executors)
         saved_hooks = [ex.on_stage_done for ex in execs]
-        self._pool = torch.cuda.graph_pool_handle()
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
         state = {"g": None, "lo": {id(ex): 0 for ex in execs}, "hi": {id(ex): 0 for ex in execs}}
@@ -530,7 +525,7 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
             with torch.cuda.stream(stream):
                 begin()
-                self.loss = fwd_bwd()
+                fwd_bwd()
                 # whatever has not been handed out yet (the tail of every bank) goes with the last segment
                 g_last = state["g"]
                 g_last.capture_end()
@@ -555,28 +550,19 @@ class GraphedTrainStep:
 
     def matches(self, z, cond_txt, hint, t, noise) -> bool:
         """Do these tensors have the shapes and dtypes the graphs were captured on?"""
-        return all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip((z, cond_txt, hint, t, noise), self._static))
+        return self._static.matches(z, cond_txt, hint, t, noise)
 
     def __call__(self, z, cond_txt, hint, t, noise):
-        if self.accumulate:
-            return self.micro(z, cond_txt, hint, t, noise)[2]
-        self.s_z.copy_(z); self.s_ctx.copy_(cond_txt); self.s_hint.copy_(hint)
-        self.s_t.copy_(t); self.s_noise.copy_(noise)
-        self.opt.sync_hyper()
-        replay_with_exchange(self.segments, self.g_b, self.opt.executors, self._reduce_fn)
+        self.micro(z, cond_txt, hint, t, noise)
         return self.loss
 
     def micro(self, z, cond_txt, hint, t, noise, first: bool = True, last: bool = True):
         """Replay one micro-step of an optimizer step and return the loss 3-vector (overwritten by the next replay).
         `first`: clear the gradients before; `last`: exchange the gradient buckets between the segments and run the optimizer
         piece after.  Without accumulate=True there is one form only, the whole optimizer step."""
-        if not self.accumulate:
-            assert first and last, "captured as one optimizer step per replay: build with accumulate=True"
-            self(z, cond_txt, hint, t, noise)
-            return self.loss3
-        self.s_z.copy_(z); self.s_ctx.copy_(cond_txt); self.s_hint.copy_(hint)
-        self.s_t.copy_(t); self.s_noise.copy_(noise)
-        if first:
+        assert self.accumulate or (first and last), "captured as one optimizer step per replay: build with accumulate=True"
+        self._static.load(z, cond_txt, hint, t, noise)
+        if first and self.g_z is not None:
             self.g_z.replay()
         if last:
             self.opt.sync_hyper()
@@ -587,17 +573,26 @@ class GraphedTrainStep:
         return self.loss3
 
 
+def _replay_step_start(g):
+    """Replay the first captured piece of an optimizer step.  The step's optimizer piece re-packs the trainables, so caches
+    of the old copies are stale: WEIGHTS_GENERATION moves before anything is enqueued."""
+    from .engine.nets import WEIGHTS_GENERATION
+    WEIGHTS_GENERATION[0] += 1
+    g.replay()
+
+
 def replay_with_exchange(segments, g_opt, execs, reduce_fn):
     """One optimizer step from captured pieces (anything with .replay()): every segment is enqueued, and right after
     a segment that completes a gradient bucket the reduction of that slice of the flat buffer is issued
     (`reduce_fn(slice)` -> handle with .wait() or None) -- it runs while the NEXT segment executes; all handles are waited for
     before the optimizer piece.  segments: [(graph, tag, lo, hi)], tag None = nothing to exchange, "all" = every executor's
     whole buffer, "tails" = lo is [(executor index, start, stop)], an int = that executor's [lo, hi) slice."""
-    from .engine.nets import WEIGHTS_GENERATION
-    WEIGHTS_GENERATION[0] += 1         # the optimizer piece re-packs the trainables: caches of the old copies are stale
     works = []
-    for g, tag, lo, hi in segments:
-        g.replay()
+    for k, (g, tag, lo, hi) in enumerate(segments):
+        if k == 0:
+            _replay_step_start(g)
+        else:
+            g.replay()
         if tag is None:
             continue
         if tag == "all":
@@ -628,8 +623,7 @@ class GraphedPretrainStep:
 
     def __init__(self, model, opt, z, cond_txt, hint, t, noise):
         self.model, self.opt = model, opt
-        self.s_z, self.s_ctx, self.s_hint = z.clone(), cond_txt.clone(), hint.clone()
-        self.s_t, self.s_noise = t.clone(), noise.clone()
+        self._static = _StaticInputs(z, cond_txt, hint, t, noise)
         self.graphs = {}             # task -> (graph, loss 3-vector)
         self._active_at_capture = None
         self._pool = None
@@ -640,15 +634,14 @@ class GraphedPretrainStep:
         cm.switch_lora(task)
         cm.executor().switch_bank(cm.bank(task), force=True)      # the graph's first kernel: this bank -> packed copies
         self.opt.zero_grad()
-        cond = {"c_crossattn": [self.s_ctx], "c_concat": [self.s_hint], "task": task}
-        loss3 = self.model.engine_train_step(self.s_z, cond, self.s_t, self.s_noise)
+        z, ctx, hint, t, noise = self._static.tensors
+        loss3 = self.model.engine_train_step(z, {"c_crossattn": [ctx], "c_concat": [hint], "task": task}, t, noise)
         self.opt.step()
         return loss3
 
     def __call__(self, task, z, cond_txt, hint, t, noise):
-        self.s_z.copy_(z); self.s_ctx.copy_(cond_txt); self.s_hint.copy_(hint)
-        self.s_t.copy_(t); self.s_noise.copy_(noise)
-        opt, cm = self.opt, self.model.control_model
+        self._static.load(z, cond_txt, hint, t, noise)
+        opt = self.opt
         if task not in opt.active:                      # the bank joins the optimizer in this step: eager
             self.eager_steps += 1
             return self._step(task)[2]
@@ -674,11 +667,6 @@ class GraphedPretrainStep:
             self.graphs[task] = (g, loss3)
             return done[2]
         opt.sync_hyper()
-        from .engine.nets import WEIGHTS_GENERATION
-        WEIGHTS_GENERATION[0] += 1
-        ent[0].replay()
-        cm._task = task
-        for lin, lora in zip(cm._lora_linears, cm.loras_dict[task]):
-            lin.set_lora_layer(lora)
-        cm.executor().switch_bank(cm.bank(task), repack=False)
+        _replay_step_start(ent[0])
+        self.model.control_model.switch_lora(task, repacked=True)
         return ent[1][2]

@@ -151,14 +151,8 @@ def test_optimizer_state_of_other_flags_is_refused():
     sd = arch.make_state(arch.controlnet_shapes(cfg), 1)
     mk = lambda nt: ControlNetE(sd, netcfg(cfg), torch.float32, torch.device("cpu"), layout_only=True, norm_trainable=nt)
     full, lean = mk(True), mk(False)
-    opts = {}
-    for key, ex in (("full", full), ("lean", lean)):
-        o = FusedAdamW.__new__(FusedAdamW)            # (the constructor pushes hyper-parameters through the HIP library)
-        o.executors, o._m, o._v = [ex], [torch.zeros_like(ex.tr.flat)], [torch.zeros_like(ex.tr.flat)]
-        o._step_dev = torch.zeros(1, dtype=torch.int32)
-        o.param_groups = []
-        o.sync_hyper = lambda: None
-        opts[key] = o
+    # (the constructor launches nothing: a layout_only executor on the CPU is enough)
+    opts = {key: FusedAdamW([torch.nn.Parameter(ex.tr.flat)], [ex]) for key, ex in (("full", full), ("lean", lean))}
     st_full, st_lean = opts["full"].state_dict(), opts["lean"].state_dict()
     st_full["step"] = st_lean["step"] = 7
     opts["full"]._m[0].fill_(3.0)

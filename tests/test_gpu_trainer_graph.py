@@ -178,6 +178,122 @@ def test_segmented_form_on_one_rank():
     _assert_same("segmented graph against eager, acc 2", (_losses(tr), _params(tr)), want)
 
 
+_FORM_REF = {}
+
+
+def _form_model():
+    m = _model().cuda().train()
+    m.set_engine_dtype(torch.float32)
+    return m, m.configure_optimizers()
+
+
+def _form_batches(acc):
+    """Three optimizer steps' worth of distinct micro-batches as (z, ctx, hint, t, noise) tuples."""
+    g = torch.Generator().manual_seed(11)
+    out = []
+    for b in _batches(3 * acc, seed=9):
+        t = torch.randint(0, 1000, (B,), generator=g).cuda()
+        out.append((b["z"], b["ctx"], b["hint_z"], t, torch.randn(B, 4, H, H, generator=g).cuda()))
+    return out
+
+
+def _form_eager_ref(acc):
+    """Three optimizer steps launched eagerly through autograd (acc micro-batches each, every loss scaled by 1 / acc for the
+    backward as the trainer does): (every micro-step's loss, every control_model parameter).  Computed once per acc."""
+    if acc not in _FORM_REF:
+        m, opt = _form_model()
+        losses = []
+        for i, (z, ctx, hint, t, noise) in enumerate(_form_batches(acc)):
+            if i % acc == 0:
+                opt.zero_grad()
+            loss, _ = m.p_losses(z, {"c_crossattn": [ctx], "c_concat": [hint]}, t, noise=noise)
+            (loss / acc).backward()
+            losses.append(float(loss.detach()))
+            if i % acc == acc - 1:
+                opt.step()
+        torch.cuda.synchronize()
+        assert int(opt._step) == 3 and len(set(losses)) == 3 * acc
+        _FORM_REF[acc] = (losses, {k: v.detach().float().cpu().clone() for k, v in m.control_model.named_parameters()})
+    return _FORM_REF[acc]
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["acc1", "acc2"])
+@pytest.mark.parametrize("split", [False, "two", "segmented"], ids=["one", "two", "segmented"])
+def test_every_capture_form_follows_eager_and_holds_the_planned_pieces(split, accumulate):
+    """GraphedTrainStep in each of its six (mode, accumulate) forms, used the way the trainer uses it: optimizer step 1 is
+    launched by eager() to warm the allocations, capture() records, steps 2 and 3 are replays.  The trajectory is the eager
+    one (the fp32 gates of test_same_trajectory_as_eager), the graphs that exist are the ones capture_plan lists, and in the
+    exchanging modes the slices handed to reduce_fn tile every flat gradient buffer exactly once per optimizer step."""
+    from ctrlora_amd.train import GraphedTrainStep, capture_plan
+    acc = 2 if accumulate else 1
+    mode = split or "one"
+    want = _form_eager_ref(acc)
+    m, opt = _form_model()
+    handed = []
+
+    def recording_identity(buf):
+        assert buf.dtype == torch.float32 and buf.is_contiguous()
+        for i, ex in enumerate(opt.executors):
+            lo = (buf.data_ptr() - ex.tr.flat_grad.data_ptr()) // 4
+            if 0 <= lo < ex.tr.flat_grad.numel():
+                handed.append((i, lo, lo + buf.numel()))
+                return None
+        raise AssertionError("reduce_fn was handed memory outside every flat gradient buffer")
+
+    batches = _form_batches(acc)
+    gs = GraphedTrainStep(m, opt, *batches[0], warmup=0, capture=False, split_graphs=split, bucket_bytes=256 << 10,
+                          reduce_fn=recording_identity, accumulate=accumulate, grad_scale=1.0 / acc)
+    assert gs.mode == mode and not gs.captured and gs.segments == []
+    losses, per_step = [], []
+    for step in range(3):
+        if step == 1:
+            gs.capture()
+            assert gs.captured and not torch.cuda.is_current_stream_capturing()
+            assert handed == [], "capturing handed a slice to reduce_fn"
+        for k in range(acc):
+            args, first, last = batches[step * acc + k], k == 0, k == acc - 1
+            if step == 0:
+                losses.append(float(gs.eager(*args, first=first, last=last)[2]))
+            elif accumulate:
+                losses.append(float(gs.micro(*args, first=first, last=last)[2]))
+            else:
+                losses.append(float(gs(*args)))
+            assert last or handed == [], "reduce_fn was called on a non-final micro-step"
+        per_step.append(sorted(handed))
+        handed.clear()
+    torch.cuda.synchronize()
+    assert int(opt._step) == 3
+
+    # the pieces: what capture_plan lists is what exists
+    plan = capture_plan(mode, accumulate)
+    kinds = [p.kind for p in plan]
+    (f,) = [p for p in plan if p.kind == "F"]
+    assert (gs.g_z is not None) == accumulate == ("Z" in kinds)
+    assert (gs.g_b is None) == (mode == "one" and not accumulate) == ("B" not in kinds) == f.with_opt
+    tags = [tag for _, tag, _, _ in gs.segments]
+    if mode == "segmented":
+        assert f.segmented and len(gs.segments) >= 3
+        assert all(isinstance(t, int) for t in tags[:-1]) and tags[-1] == "tails"
+    else:
+        assert not f.segmented and len(gs.segments) == 1 and tags == [f.tag]
+    # the exchange: nothing on one rank in one graph, else every slice of every buffer once per optimizer step
+    for step, spans in enumerate(per_step):
+        if mode == "one":
+            assert spans == []
+            continue
+        for i, ex in enumerate(opt.executors):
+            pos = 0
+            for _, lo, hi in [s for s in spans if s[0] == i]:
+                assert lo == pos and hi > lo, f"optimizer step {step + 1}: slices {spans} do not tile executor {i}'s buffer"
+                pos = hi
+            assert pos == ex.tr.flat_grad.numel(), f"optimizer step {step + 1}: slices {spans} do not tile executor {i}'s buffer"
+    if mode == "segmented":
+        assert len(per_step[1]) == len(per_step[2]) > 1, "one bucket only: the segmented exchange was not exercised"
+    print(f"[trainer graph] form ({mode}, acc {acc}): {len(gs.segments)} F graph(s), slices per step {[len(s) for s in per_step]}")
+    got = (losses, {k: v.detach().float().cpu().clone() for k, v in m.control_model.named_parameters()})
+    _assert_same(f"form ({mode}, acc {acc}) against eager", got, want)
+
+
 def test_work_between_replays():
     """After optimizer step 3 a callback samples with DDIM in eval mode (both legs); training goes on to step 6 on the eager
     trajectory and both legs' samples agree: the sampler saw the replayed weights and did not disturb the capture."""
