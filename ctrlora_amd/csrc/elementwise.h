@@ -9,14 +9,15 @@ namespace cl {
 // call leaves id = 0.  form / aux: colsum 1 = block partials + finishing kernel, 2 = atomics, aux = pixel chunks; zero: bit 0 =
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
 // transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
-// qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel.
+// qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel; grad_norm: the partial
+// launch's grid, aux = buffers.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
   EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
   EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV,
-  EW_QSAMPLE_BLEND
+  EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP
 };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
@@ -59,6 +60,13 @@ int ddim_step(const float* x, const float* e_c, const float* e_u, const float* n
               float scale, float* x_prev, float* pred_x0, long n, hipStream_t st);
 int tick(int* counter, hipStream_t st);
 int adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, hipStream_t st);
+// global L2 norm of up to 16 flat fp32 buffers times hyper[5], and torch's clip coefficient, to out[0..1]; AdamW on the
+// clipped gradient (elementwise.hip)
+long grad_norm_scratch_floats(int nbuf);
+int grad_norm(const float* const* bufs, const long* counts, int nbuf, const float* hyper, const float* max_norm, float* out,
+              float* scratch, hipStream_t st);
+int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
+                   hipStream_t st);
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st);
 int ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                   const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, hipStream_t st);

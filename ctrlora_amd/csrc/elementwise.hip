@@ -470,6 +470,90 @@ __global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------- global gradient norm + clip coefficient
+// torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite=False) over up to GN_MAX_BUFS flat fp32 buffers, in two
+// launches and no atomics (the plosses pattern above): workgroup w strides over every buffer in turn and leaves ONE fp64 partial
+// in scratch[w]; the finishing workgroup adds the partials in index order.  The squares are formed and summed in fp64 from the
+// first product on: g^2 neither overflows nor underflows, and the rounding of the sum stays far below one fp32 ulp for any n the
+// engine can hold, so the result does not depend on how the elements were split over threads beyond that.  The order is fixed by
+// the launch geometry alone: a replay gives the same bits.  The kernel is bound by its 4 B / element read.
+//   out[0] = hyper[5] * sqrt(sum g^2)      (grad_scale: the norm of the gradient AdamW applies)
+//   out[1] = coef = max_norm <= 0 ? 1 : clamp(max_norm / (out[0] + 1e-6), max = 1), NaN kept as torch.clamp keeps it
+// A buffer is read with 16-byte loads from its first 16-byte boundary on; the elements before it (head) and the last n % 4 after
+// the vectors (tail) are read one by one by the first threads of the grid, as zero_kernel does.
+constexpr int GN_MAX_BUFS = 16;
+constexpr int GN_MAX_GROUPS = 512;     // workgroups of the partial launch = fp64 partials the finishing workgroup adds
+struct GradNormBufs {
+  const float* p[GN_MAX_BUFS];
+  long n[GN_MAX_BUFS];
+};
+__device__ __forceinline__ double gn_sq4(const float4 a) {
+  return ((double)a.x * (double)a.x + (double)a.y * (double)a.y) + ((double)a.z * (double)a.z + (double)a.w * (double)a.w);
+}
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const GradNormBufs bufs, int nbuf, double* __restrict__ scratch) {
+  __shared__ double red[4];
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  double acc = 0.0;
+  for (int b = 0; b < nbuf; ++b) {
+    const float* __restrict__ p = bufs.p[b];
+    const long n = bufs.n[b];
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long nvec = (n - head) >> 2, tail = n - head - (nvec << 2);
+    const float4* __restrict__ body = reinterpret_cast<const float4*>(p + head);
+    long i = gid;
+    for (; i + 3 * stride < nvec; i += 4 * stride) {     // four independent 16-byte loads in flight per thread
+      const float4 a0 = body[i], a1 = body[i + stride], a2 = body[i + 2 * stride], a3 = body[i + 3 * stride];
+      acc += (gn_sq4(a0) + gn_sq4(a1)) + (gn_sq4(a2) + gn_sq4(a3));
+    }
+    for (; i < nvec; i += stride) acc += gn_sq4(body[i]);
+    if (gid < head) { const double g = (double)p[gid]; acc += g * g; }
+    if (gid < tail) { const double g = (double)p[head + (nvec << 2) + gid]; acc += g * g; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) scratch[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ scratch, int groups,
+                                                               const float* __restrict__ hyper,
+                                                               const float* __restrict__ max_norm, float* __restrict__ out) {
+  __shared__ double part[GN_MAX_GROUPS];
+  for (int i = threadIdx.x; i < groups; i += 256) part[i] = scratch[i];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int i = 0; i < groups; ++i) s += part[i];
+  const float norm = (float)((double)hyper[5] * sqrt(s));
+  float coef = 1.0f;
+  const float mx = max_norm ? *max_norm : 0.0f;
+  if (!(mx <= 0.0f)) {
+    const float c = mx / (norm + 1e-6f);
+    coef = c < 1.0f ? c : (c != c ? c : 1.0f);
+  }
+  out[0] = norm; out[1] = coef;
+}
+
+// adamw_dev_kernel on the clipped gradient: gi = g[i] * (grad_scale * coef), clip = grad_norm_finish_kernel's out.  The two
+// scalars are multiplied FIRST: with coef == 1.0f the product is grad_scale itself and every bit equals adamw_dev_kernel's.
+__global__ void adamw_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                      float* __restrict__ v, long n, const float* __restrict__ hyper,
+                                      const int* __restrict__ step, const float* __restrict__ clip) {
+  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5] * clip[1];
+  const float st = (float)*step;
+  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gi = g[i] * gscale;
+    float pi = p[i] * (1.0f - lr * wd);
+    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * mi / denom;
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
 // DDIM loop with a device cursor i = 0..S-1 (ddim_hacked.py:157-160): index = S-1-i, ts = ddim_timesteps[index]
 __global__ void ddim_set_t_kernel(const long* __restrict__ table, const int* __restrict__ cursor, int S,
                                   long* __restrict__ ts, int n) {
@@ -1096,6 +1180,38 @@ int adamw_dev(float* p, const float* g, float* m, float* v, long n, const float*
   const dim3 grid(ew_grid(n));
   hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step);
   return ew_done(EW_ADAMW_DEV, -1, grid, 256);
+}
+long grad_norm_scratch_floats(int nbuf) {
+  if (nbuf < 1 || nbuf > GN_MAX_BUFS) return 0;
+  return 2L * GN_MAX_GROUPS;      // one fp64 partial per workgroup, whatever the number of buffers
+}
+int grad_norm(const float* const* bufs, const long* counts, int nbuf, const float* hyper, const float* max_norm, float* out,
+              float* scratch, hipStream_t st) {
+  ew_rec_begin();
+  if (nbuf < 1 || nbuf > GN_MAX_BUFS || !bufs || !counts || !hyper || !out || !scratch) return CL_EINVAL;
+  if (reinterpret_cast<uintptr_t>(scratch) & 7) return CL_EINVAL;        // the partials are fp64
+  GradNormBufs a{};
+  long total = 0;
+  for (int b = 0; b < nbuf; ++b) {
+    if (counts[b] < 0 || (counts[b] > 0 && !bufs[b]) || (reinterpret_cast<uintptr_t>(bufs[b]) & 3)) return CL_EINVAL;
+    a.p[b] = bufs[b]; a.n[b] = counts[b];
+    total += counts[b];
+  }
+  long groups = (total + 1023) / 1024;             // a workgroup's trip covers 256 x 4 elements
+  groups = groups < 1 ? 1 : groups > GN_MAX_GROUPS ? GN_MAX_GROUPS : groups;
+  const dim3 grid((unsigned)groups);
+  hipLaunchKernelGGL(grad_norm_partial_kernel, grid, dim3(256), 0, st, a, nbuf, reinterpret_cast<double*>(scratch));
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const double*>(scratch), (int)groups,
+                     hyper, max_norm, out);
+  return ew_done(EW_GRAD_NORM, -1, grid, 256, 0, nbuf);
+}
+int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
+                   hipStream_t st) {
+  ew_rec_begin();
+  if (n < 0 || !hyper || !step || !clip || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));
+  hipLaunchKernelGGL(adamw_dev_clip_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step, clip);
+  return ew_done(EW_ADAMW_DEV_CLIP, -1, grid, 256);
 }
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st) {
   ew_rec_begin();

@@ -126,7 +126,11 @@ _SIGS = {
     "cl_plms_step": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "cl_plms_step_dev": [_P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _L, _P],
     "cl_qsample_blend": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _I, _L, _P],
+    "cl_grad_norm_scratch_floats": [_I],
+    "cl_grad_norm": [_P, _P, _I, _P, _P, _P, _P, _P],
+    "cl_adamw_dev_clip": [_P, _P, _P, _P, _L, _P, _P, _P, _P],
 }
+_LONG_RESULT = ("cl_groupnorm_ws_floats", "cl_grad_norm_scratch_floats")
 EXPORTED = tuple(_SIGS.keys())
 # probe hooks (ctrlora_amd/csrc/debug_hooks.h): exported by the library, not part of include/ctrlora_hip.h
 _DEBUG_SIGS = {
@@ -162,7 +166,7 @@ def lib():
         for name, args in {**_SIGS, **_DEBUG_SIGS}.items():
             fn = getattr(L, name)
             fn.argtypes = args
-            fn.restype = C.c_long if name == "cl_groupnorm_ws_floats" else C.c_int
+            fn.restype = C.c_long if name in _LONG_RESULT else C.c_int
         _lib = L
         if os.environ.get("CTRLORA_ATTN_FUSE_DELTA", "1") == "0":      # A/B switch: separate attn_delta launch
             L.cl_debug_attention_fuse_delta(0)
@@ -811,6 +815,32 @@ def adamw_dev(p, g, m, v, hyper, step):
     tick() ONCE per optimizer step, before the first bank."""
     _chk(lib().cl_adamw_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(),
                             step.data_ptr(), stream()), "cl_adamw_dev")
+
+
+GRAD_NORM_MAX_BUFS = 16
+
+
+def grad_norm_scratch_floats(nbuf=1):
+    return int(lib().cl_grad_norm_scratch_floats(nbuf))
+
+
+def grad_norm(bufs, hyper, max_norm, out, scratch):
+    """out[0] = hyper[5] * ||concat(bufs)||_2, out[1] = torch's clip coefficient for the device threshold `max_norm` (None or
+    <= 0: tracking only, coef = 1).  bufs: up to 16 flat fp32 tensors.  Two launches, no host sync: capturable."""
+    n = len(bufs)
+    for b in bufs:
+        assert b.dtype == torch.float32 and b.is_contiguous(), (b.dtype, b.stride())
+    ptrs = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in bufs])
+    counts = (C.c_long * max(n, 1))(*[b.numel() for b in bufs])
+    _chk(lib().cl_grad_norm(ptrs, counts, n, hyper.data_ptr(), ptr(max_norm), out.data_ptr(), scratch.data_ptr(), stream()),
+         "cl_grad_norm")
+    return out
+
+
+def adamw_dev_clip(p, g, m, v, hyper, step, clip):
+    """adamw_dev on g * (grad_scale * clip[1]); clip = grad_norm's out.  clip[1] == 1 gives adamw_dev's bits."""
+    _chk(lib().cl_adamw_dev_clip(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(),
+                                 step.data_ptr(), clip.data_ptr(), stream()), "cl_adamw_dev_clip")
 
 
 def ddim_set_t(table, cursor, S, ts):

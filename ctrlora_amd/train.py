@@ -179,13 +179,24 @@ class _FlatAdamW(torch.optim.Optimizer):
     """What the two optimizers over the engine's flat buffers share; a subclass launches its kernels in `_update()` and
     `zero_grad()`.  `params` are the bound nn.Parameters (kept in param_groups for scheduler / checkpoint compatibility); step
     counts and hyper-parameters live in DEVICE memory (cl_adamw_dev), so that `step()` can be captured in a hipGraph and
-    replayed: a schedule only has to refresh the 6-float `hyper` tensor (`sync_hyper()`, automatic outside capture)."""
+    replayed: a schedule only has to refresh the 6-float `hyper` tensor (`sync_hyper()`, automatic outside capture).
+
+    Global gradient norm (torch.nn.utils.clip_grad_norm_ with norm_type 2, on the device): `max_grad_norm` (None or <= 0: off)
+    clips, `track_grad_norm` measures without clipping.  With either on, `_update()` opens with cl_grad_norm over the buffers the
+    step updates and runs cl_adamw_dev_clip in place of cl_adamw_dev; `last_grad_norm()` returns (norm, coef) as device tensors.
+    The threshold lives in device memory and follows `sync_hyper()`'s rule, so a schedule may move it between replays.  Turning
+    the feature on or off changes what is launched: do it before a capture, not after.  With both off nothing changes."""
 
     def __init__(self, params, device, lr, betas, eps, weight_decay, grad_scale):
         super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = grad_scale
         self._hyper = torch.zeros(6, dtype=torch.float32, device=device)
         self._hyper_host = None
+        self.max_grad_norm, self.track_grad_norm = None, False
+        self._max_norm = torch.zeros(1, dtype=torch.float32, device=device)      # the threshold; 0 = tracking only
+        self._max_norm_host = 0.0
+        self.grad_norm_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=device)     # {norm, coef} of the last step
+        self._norm_scratch = None
         self.pre_step_hook = None     # e.g. DP: wait for the gradient all-reduce
         self.sync_hyper()
 
@@ -198,6 +209,31 @@ class _FlatAdamW(torch.optim.Optimizer):
         if cur != self._hyper_host:
             self._hyper.copy_(torch.tensor(cur, dtype=torch.float32))
             self._hyper_host = cur
+        mx = float(self.max_grad_norm) if self.max_grad_norm is not None and self.max_grad_norm > 0 else 0.0
+        if mx != self._max_norm_host:
+            self._max_norm.copy_(torch.tensor([mx], dtype=torch.float32))
+            self._max_norm_host = mx
+        if self.norm_enabled and self._norm_scratch is None:      # allocated here: never inside a capture
+            self._norm_scratch = torch.empty(hip.grad_norm_scratch_floats(), dtype=torch.float32, device=self._hyper.device)
+
+    @property
+    def norm_enabled(self) -> bool:
+        return bool(self.track_grad_norm) or (self.max_grad_norm is not None and self.max_grad_norm > 0)
+
+    def last_grad_norm(self):
+        """(norm, coef) of the last step as device tensors (views of `grad_norm_out`; no synchronization): the norm of
+        grad_scale x the gradient before clipping, and the factor the step applied (1 when it did not clip)."""
+        return self.grad_norm_out[0], self.grad_norm_out[1]
+
+    def _grad_norm(self, bufs) -> bool:
+        """Opens `_update()`: with the norm on, launch cl_grad_norm over `bufs` into `grad_norm_out` and return True."""
+        if not self.norm_enabled:
+            return False
+        if len(bufs) > hip.GRAD_NORM_MAX_BUFS:
+            raise ValueError(f"the gradient norm covers at most {hip.GRAD_NORM_MAX_BUFS} flat buffers, the step has {len(bufs)}")
+        assert self._norm_scratch is not None, "sync_hyper() has not run since the gradient norm was turned on"
+        hip.grad_norm(bufs, self._hyper, self._max_norm, self.grad_norm_out, self._norm_scratch)
+        return True
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -237,9 +273,13 @@ class FusedAdamW(_FlatAdamW):
     _v = property(lambda self: [st.v for st in self._states])
 
     def _update(self):
+        clip = self._grad_norm([ex.tr.flat_grad for ex in self.executors])
         hip.tick(self._step_dev)          # one tick per optimizer step, however many banks follow
         for ex, st in zip(self.executors, self._states):
-            hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
+            if clip:
+                hip.adamw_dev_clip(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev, self.grad_norm_out)
+            else:
+                hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
             ex.repack()
 
     def zero_grad(self, set_to_none: bool = False):
@@ -285,9 +325,16 @@ class PretrainAdamW(_FlatAdamW):
     _step = property(lambda self: int(self._base.step.item()))
 
     def _update(self):
-        for ts, st in [(self.executor.tr, self._base)] + [(self.banks[k], self._bank_state[k]) for k in self.active]:
+        sets = [(self.executor.tr, self._base)] + [(self.banks[k], self._bank_state[k]) for k in self.active]
+        # the norm runs over the parameters whose .grad is not None in the reference: the base and every active bank, an idle
+        # one with its zero gradient
+        clip = self._grad_norm([ts.flat_grad for ts, _ in sets])
+        for ts, st in sets:
             hip.tick(st.step)
-            hip.adamw_dev(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step)
+            if clip:
+                hip.adamw_dev_clip(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step, self.grad_norm_out)
+            else:
+                hip.adamw_dev(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step)
         self.executor.repack()
 
     def zero_grad(self, set_to_none: bool = False):

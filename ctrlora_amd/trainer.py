@@ -13,6 +13,12 @@ Semantics kept from Lightning 1.5: the loss of each micro-batch is divided by `a
 after every micro-batch and `on_batch_end(trainer, module)` (what `CheckpointEveryNSteps` hooks); checkpoints are
 `{"state_dict", "global_step", "epoch", "optimizer_states"}` and resumable with `fit(..., ckpt_path=)`.
 
+`gradient_clip_val` / `gradient_clip_algorithm` / `track_grad_norm` carry Lightning 1.5's names: clipping by the global L2
+norm of the gradients before the optimizer step (once per optimizer step, after the exchange and the last accumulation
+micro-step), and / or tracking that norm as `train/grad_norm`.  The engine's optimizers do both on the device inside their own
+step (`ctrlora_amd.train._FlatAdamW`), so it replays with the rest of a captured step; any other optimizer goes through
+`torch.nn.utils.clip_grad_norm_`.  Clipping by value is not offered.
+
 `graph_step=True` (LoRA fine-tuning on a GPU only; off by default) replays the optimizer step as hipGraphs
 (`ctrlora_amd.train.GraphedTrainStep`) instead of launching its ~1900 kernels one by one: see `Trainer._fit_graphed`.
 """
@@ -54,8 +60,19 @@ class Trainer:
     def __init__(self, max_steps: int = 100000, accumulate_grad_batches: int = 1, precision=32,
                  callbacks: Sequence = (), default_root_dir: str = "runs/default", device: Optional[str] = None,
                  strategy: str = "ddp", accelerator: str = "gpu", devices=-1, log_every_n_steps: int = 50,
-                 graph_step=False):
+                 graph_step=False, gradient_clip_val=None, gradient_clip_algorithm: str = "norm", track_grad_norm=-1):
         self.max_steps = int(max_steps)
+        if gradient_clip_algorithm != "norm":
+            raise ValueError(f"gradient_clip_algorithm='{gradient_clip_algorithm}' is not supported: gradients are clipped by their "
+                             "global L2 norm only ('norm'); clipping by value is not offered")
+        if track_grad_norm not in (-1, 2, 2.0):
+            raise ValueError(f"track_grad_norm={track_grad_norm!r}: -1 (off) or 2 (the L2 norm) only")
+        if gradient_clip_val is not None and not float(gradient_clip_val) >= 0.0:
+            raise ValueError(f"gradient_clip_val={gradient_clip_val!r} must be None or >= 0 (0 = off)")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else 0.0      # 0.0 = off
+        self.track_grad_norm = track_grad_norm != -1
+        self._norm_on = self._norm_in_opt = False       # decided in fit(), once the optimizer exists
+        self.logged_grad_norm = []      # (global_step, norm) at log_every_n_steps, where the loss is read too
         self.accumulate_grad_batches = max(1, int(accumulate_grad_batches))
         self.precision = precision
         self.callbacks = list(callbacks)
@@ -164,6 +181,9 @@ class Trainer:
         self.optimizer = opt[0] if isinstance(opt, (list, tuple)) else opt
         if ck is not None:
             self._restore_optimizer(ck)
+        self._set_up_grad_norm()
+        if self.graph_step and self._norm_on and not self._norm_in_opt:
+            raise ValueError(f"graph_step with gradient clipping needs an engine optimizer, not {type(self.optimizer).__name__}")
         if self.graph_step:
             return self._fit_graphed(model, train_dataloader)
         acc = self.accumulate_grad_batches
@@ -184,10 +204,15 @@ class Trainer:
                 (loss / acc).backward()
                 micro += 1
                 if last:
+                    norm = self._clip_torch() if self._norm_on and not self._norm_in_opt else None
                     self.optimizer.step()
+                    if self._norm_in_opt:
+                        norm = self.optimizer.last_grad_norm()[0]
                     self.optimizer.zero_grad()
                     self.global_step += 1
                     model.global_step = self.global_step
+                    if self.global_step % self.log_every_n_steps == 0:
+                        self._log_grad_norm(model, norm, self.global_step)
                     if self.is_global_zero and self.global_step % self.log_every_n_steps == 0:
                         self.logged.append((self.global_step, float(loss.detach())))
                         print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss.detach()):.5f}")
@@ -201,6 +226,35 @@ class Trainer:
             model.current_epoch = self.current_epoch
         self._call("on_train_end", model)
         return self
+
+    # ------------------------------------------------------------------ gradient norm: clip and / or track
+    def _set_up_grad_norm(self):
+        """Before the first step: an engine optimizer takes the settings and does the work inside its own step (eager or
+        captured); any other optimizer is clipped by `_clip_torch` in the eager loop."""
+        from ctrlora_amd.train import _FlatAdamW
+        self._norm_on = self.gradient_clip_val > 0.0 or self.track_grad_norm
+        self._norm_in_opt = self._norm_on and isinstance(self.optimizer, _FlatAdamW)
+        if self._norm_in_opt:
+            self.optimizer.max_grad_norm = self.gradient_clip_val if self.gradient_clip_val > 0.0 else None
+            self.optimizer.track_grad_norm = self.track_grad_norm
+            self.optimizer.sync_hyper()
+
+    def _clip_torch(self):
+        """torch.nn.utils.clip_grad_norm_ over the optimizer's parameters; tracking alone measures with an infinite threshold."""
+        params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+        max_norm = self.gradient_clip_val if self.gradient_clip_val > 0.0 else float("inf")
+        return torch.nn.utils.clip_grad_norm_(params, max_norm)
+
+    def _log_grad_norm(self, model, norm, step, extra=None):
+        """`train/grad_norm` of optimizer step `step` through the model's log_dict (with `extra`, or else with what the model
+        logged last): called at the steps where the loss is read on the host already."""
+        if norm is None:
+            return
+        norm = float(norm)
+        self.logged_grad_norm.append((step, norm))
+        if callable(getattr(model, "log_dict", None)):
+            prev = extra if extra is not None else getattr(model, "last_logged", None)
+            model.log_dict({**(prev if isinstance(prev, dict) else {}), "train/grad_norm": norm})
 
     # ------------------------------------------------------------------ the loop, optimizer step as hipGraph replays
     def _make_graph_step(self, model, tensors):
@@ -261,7 +315,11 @@ class Trainer:
                 micro += 1
                 loss3 = loss3.clone()                   # a replay overwrites its output: callbacks may keep theirs
                 loss = loss3[2]
-                model.log_dict({"train/loss_simple": loss3[0], "train/loss_vlb": loss3[1], "train/loss": loss})
+                losses = {"train/loss_simple": loss3[0], "train/loss_vlb": loss3[1], "train/loss": loss}
+                if last and self._norm_in_opt and (self.global_step + 1) % self.log_every_n_steps == 0:
+                    self._log_grad_norm(model, self.optimizer.last_grad_norm()[0], self.global_step + 1, extra=losses)
+                else:
+                    model.log_dict(losses)
                 if last:
                     self.global_step += 1
                     steps_here += 1

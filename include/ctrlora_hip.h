@@ -472,6 +472,27 @@ int cl_adamw(float* p, const float* g, float* m, float* v, long n, float lr, flo
  * (cldm/ddim_hacked.py:157-160,203-231); x_prev may alias x. */
 int cl_tick(int* counter, void* stream);
 int cl_adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, void* stream);
+/* Global gradient norm and clip coefficient on the device, added in ABI 7 (compatible): torch.nn.utils.clip_grad_norm_ (L2,
+ * error_if_nonfinite=False) over nbuf (1 .. 16) flat fp32 buffers, with no host round trip, so that it replays inside a hipGraph.
+ * bufs / counts are HOST arrays of nbuf device pointers / element counts (copied into the launch); hyper is cl_adamw_dev's table.
+ *   out[0] = hyper[5] * sqrt(sum over all buffers of g^2)     -- grad_scale: the norm of the gradient AdamW applies
+ *   out[1] = coef:  1.0f exactly when max_norm is NULL or *max_norm <= 0 (tracking only); otherwise, in fp32,
+ *            c = *max_norm / (out[0] + 1e-6f),  coef = c < 1 ? c : (c != c ? c : 1.0f)   -- torch.clamp(c, max=1.0), NaN kept
+ * Two launches: workgroups stride over the buffers (16-byte loads from each buffer's first 16-byte boundary, scalar head and
+ * tail) and leave one fp64 partial each in scratch; one finishing workgroup adds them in index order.  Squares and sums are fp64
+ * from the first product on.  No atomics, no waiting: the same bits on every launch and replay.  A non-finite element gives a
+ * non-finite norm (NaN -> coef NaN, +-inf -> coef 0), as torch propagates it.  scratch: cl_grad_norm_scratch_floats(nbuf) floats,
+ * 8-byte aligned (0 for an nbuf outside 1 .. 16).
+ * Refused, before anything is launched: nbuf outside 1 .. 16, a negative count, a null buffer with a positive count, a buffer not
+ * 4-byte aligned, a null bufs / counts / hyper / out / scratch, scratch not 8-byte aligned.  A count of 0 is fine (the norm of
+ * nothing is 0).
+ * cl_adamw_dev_clip: cl_adamw_dev with gi = g[i] * (hyper[5] * clip[1]), clip = the out of cl_grad_norm; the two scalars are
+ * multiplied first, so clip[1] == 1.0f gives cl_adamw_dev's bits.  Refusals as cl_adamw_dev, and a null clip. */
+long cl_grad_norm_scratch_floats(int nbuf);
+int cl_grad_norm(const float* const* bufs, const long* counts, int nbuf, const float* hyper, const float* max_norm, float* out,
+                 float* scratch, void* stream);
+int cl_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
+                      void* stream);
 int cl_ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, void* stream);
 int cl_ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                      const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, void* stream);

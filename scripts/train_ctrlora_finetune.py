@@ -53,6 +53,11 @@ def get_parser():
                         "hipGraphs after two eagerly launched steps and replay it for every later batch instead of launching its "
                         "~1900 kernels from Python; the data loading, the first stage and the text encoder stay outside the "
                         "capture (GPU only; works with --latent_cache, --gradacc and torchrun; off by default)")
+    p.add_argument("--grad_clip", type=float, default=0.0,
+                   help="clip the global L2 norm of the gradients to this value before every optimizer step, on the device and "
+                        "inside the step (Trainer(gradient_clip_val=)); 0 = off (the default)")
+    p.add_argument("--track_grad_norm", action="store_true", default=False,
+                   help="log the global L2 norm of the gradients as train/grad_norm without clipping (off by default)")
     return p
 
 
@@ -139,11 +144,14 @@ def main(argv=None):
     trainer = Trainer(max_steps=args.max_steps, accumulate_grad_batches=args.gradacc, precision=args.precision,
                       callbacks=[ImageLogger(batch_frequency=args.img_logger_freq),
                                  CheckpointEveryNSteps(save_step_frequency=args.ckpt_logger_freq)],
-                      default_root_dir=os.path.join("runs", name), graph_step=bool(args.graph))
+                      default_root_dir=os.path.join("runs", name), graph_step=bool(args.graph),
+                      gradient_clip_val=args.grad_clip or None, track_grad_norm=2 if args.track_grad_norm else -1)
     trainer.fit(model, loader)
     if args.graph and rank == 0:
         print(f"[trainer] graph mode '{trainer.graph_mode}': {trainer.graph_replays} optimizer steps replayed, "
               f"{trainer.graph_eager_steps} launched eagerly")
+    if trainer.logged_grad_norm and rank == 0:
+        print(f"[trainer] train/grad_norm at step {trainer.logged_grad_norm[-1][0]}: {trainer.logged_grad_norm[-1][1]:.5f}")
     return trainer
 
 

@@ -35,6 +35,11 @@ def get_parser():
     p.add_argument("--img_logger_freq", type=int, default=10000, help="img logger freq")
     p.add_argument("--ckpt_logger_freq", type=int, default=10000, help="ckpt logger freq")
     p.add_argument("--num_workers", type=int, default=16)
+    p.add_argument("--grad_clip", type=float, default=0.0,
+                   help="clip the global L2 norm of the gradients to this value before every optimizer step, on the device and "
+                        "inside the step (Trainer(gradient_clip_val=)); 0 = off (the default)")
+    p.add_argument("--track_grad_norm", action="store_true", default=False,
+                   help="log the global L2 norm of the gradients as train/grad_norm without clipping (off by default)")
     return p
 
 
@@ -102,7 +107,8 @@ def main(argv=None):
     trainer = Trainer(max_steps=args.max_steps, accumulate_grad_batches=args.gradacc, precision=args.precision,
                       callbacks=[ImageLogger(batch_frequency=args.img_logger_freq),
                                  CheckpointEveryNSteps(save_step_frequency=args.ckpt_logger_freq)],
-                      default_root_dir=os.path.join("runs", name))
+                      default_root_dir=os.path.join("runs", name),
+                      gradient_clip_val=args.grad_clip or None, track_grad_norm=2 if args.track_grad_norm else -1)
     trainer.fit(model, loader)
 
 
