@@ -4,7 +4,8 @@
     fp64 torch of the reference's IPCrossAttention arithmetic (ldm/modules/attention_ip.py:196-289 of the reference: two
     separate softmaxes, out = softmax(s q k^T) v + ip_scale * softmax(s q k_ip^T) v_ip) at every d_head of the forward
     family, the SD1.5 query counts, 77 text keys, Nip in {1, 4, 16, 64}, ip_scale in {0, 0.5, 1}; bf16 gated by the
-    error of the plain cl_attention_fwd_v2 at the same shape, measured in the same test;
+    error of the plain cl_attention_fwd_v2 at the same shape, measured in the same test (the element-wise conformance suite
+    of both kernels -- layouts, canaries, launch forms -- is tests/test_gpu_attention_ip_conformance.py);
   * the engine: with every ip_scale at 0 or without image-prompt tokens, eps is torch.equal to the plain UNet's; with
     them, the image-prompt layers change eps and bf16 follows fp32.
 """
