@@ -118,6 +118,8 @@ class ControlLDM(LatentDiffusion):
         self.sd_locked = True
         self.engine_dtype = None
         self.dp = None   # ctrlora_amd.parallel.GradAllReduce when running data parallel
+        if self.use_ema:
+            self._build_ema()      # the subclass with supports_ema: shadows of what it trains, now that control_model exists
 
     # ---- engine plumbing
     def set_engine_dtype(self, dtype):
@@ -279,10 +281,15 @@ class ControlLDM(LatentDiffusion):
 
     @torch.no_grad()
     def log_images(self, batch, N=4, n_row=2, sample=False, ddim_steps=50, ddim_eta=0.0, unconditional_guidance_scale=9.0,
-                   **kwargs):
+                   use_ema_scope=True, **kwargs):
         """What ImageLogger writes during training (cldm/cldm.py:359-411, cldm_ctrlora_pretrain.py:113-172): the VAE
         reconstruction of the target, the condition image, the caption, and DDIM samples with classifier-free guidance,
-        all through the engine (sample_log -> DDIMSampler, decode_first_stage)."""
+        all through the engine (sample_log -> DDIMSampler, decode_first_stage).  `use_ema_scope` (ddpm.py:1256 of the
+        reference): with use_ema the samples are drawn from the EMA weights; without it the scope is a no-op."""
+        with (self.ema_scope() if use_ema_scope else contextlib.nullcontext()):
+            return self._log_images(batch, N, sample, ddim_steps, ddim_eta, unconditional_guidance_scale)
+
+    def _log_images(self, batch, N, sample, ddim_steps, ddim_eta, unconditional_guidance_scale):
         from ldm.util import log_txt_as_img
         z, c = self.get_input(batch, self.first_stage_key, bs=N)
         N = min(z.shape[0], N)

@@ -58,6 +58,71 @@ class ControlNetFinetune(ControlNet):
 
 
 class ControlFinetuneLDM(ControlLDM):
+    """`use_ema: True` (with `ema_decay`, default LitEma's 0.9999) keeps an exponential moving average of the TRAINED weights
+    in `self.model_ema` (ldm.modules.ema.ModelEma: LitEma's buffers, key rule and arithmetic).  Two deliberate differences from
+    the reference's wiring (ddpm.py:85-88, 194-207, 441-443), which shadows `self.model` -- the frozen UNet -- from its
+    construction-time values: the shadowed set is `trainable_names()`, what `configure_optimizers()` hands to FusedAdamW, and a
+    load_state_dict whose source carries no `model_ema.*` key re-seeds the shadows from the loaded weights (the reference's
+    reset_ema).  The update runs once per OPTIMIZER step, inside the optimizer's own step (the reference's on_train_batch_end
+    runs after every micro-batch)."""
+    supports_ema = True
+
+    # ---- EMA of the trained weights
+    def _ema_named_params(self):
+        """Model-relative name -> Parameter of the shadowed set, in trainable_names() order."""
+        params = dict(self.control_model.named_parameters())
+        return {"control_model." + n: params[n] for n in self.trainable_names()}
+
+    def _build_ema(self):
+        from ldm.modules.ema import ModelEma
+        self.model_ema = ModelEma(self._ema_named_params(), decay=self.ema_decay)
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._ema_after_load())
+
+    def _ema_after_load(self):
+        if self.model_ema.source_had_keys():
+            self.model_ema.touched = True      # restored like any buffer
+        else:
+            done = int(self.model_ema.num_updates)
+            if done > 0:
+                print(f"[ema] load_state_dict without model_ema.* keys: the average of {done} updates is discarded, the shadows "
+                      "start again from the loaded weights")
+            self.reseed_ema()
+
+    @torch.no_grad()
+    def reseed_ema(self):
+        """Shadows := the trained weights as they are now, num_updates := 0."""
+        self.model_ema.seed(self._ema_named_params())
+
+    def _bind_ema(self):
+        """With the executor built: the shadows as views of one flat buffer laid out like its flat masters (idempotent)."""
+        ex = self.control_model.executor()
+        return ex, self.model_ema.bind(ex, prefix="control_model.")
+
+    def _ema_enter(self):
+        ema = self.model_ema
+        if ema.in_scope:
+            raise RuntimeError("ema_scope() is not re-entrant")
+        if self.device.type == "cuda":
+            from ctrlora_amd import hip
+            ex, shadow = self._bind_ema()
+            hip.swap_(ex.tr.flat, shadow)      # no tensor moves: a step captured before the scope replays correctly after it
+            ex.repack()
+        else:
+            params = list(self._ema_named_params().values())
+            ema.store(params)
+            ema.copy_to(self._ema_named_params())
+        ema.in_scope = True
+
+    def _ema_exit(self):
+        ema = self.model_ema
+        if self.device.type == "cuda":
+            from ctrlora_amd import hip
+            ex, shadow = self._bind_ema()
+            hip.swap_(ex.tr.flat, shadow)
+            ex.repack()
+        else:
+            ema.restore(list(self._ema_named_params().values()))
+        ema.in_scope = False
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
@@ -139,4 +204,6 @@ class ControlFinetuneLDM(ControlLDM):
         opt = FusedAdamW(params, [ex], lr=self.learning_rate, grad_scale=1.0 / world)
         if self.dp is not None:
             opt.pre_step_hook = self.dp.wait
+        if self.use_ema:
+            opt.attach_ema(self.model_ema, [self._bind_ema()[1]])
         return opt

@@ -32,8 +32,9 @@ def load_state_dict(ckpt_path, location="cpu"):
     return tensors
 
 
-def create_model(config_path):
-    """cldm/model.py:23-28.  The parameters come out with torch's default distributions, drawn the fast way
+def create_model(config_path, params=None):
+    """cldm/model.py:23-28; `params` (not in the reference) overrides entries of the config's model.params, for what a script
+    sets from its command line (use_ema / ema_decay).  The parameters come out with torch's default distributions, drawn the fast way
     (ctrlora_amd/fastinit.py: a checkpoint overwrites them in every script anyway, and eight ranks constructing the model with
     per-layer kaiming_uniform_ calls spend minutes of shared host cores).  CTRLORA_FAST_INIT=0 keeps torch's own per-layer
     draws (as bench.build_model does)."""
@@ -41,11 +42,15 @@ def create_model(config_path):
     from ctrlora_amd.fastinit import fill_default_init, skip_default_init
     with open(config_path) as fh:
         tree = yaml.safe_load(fh)
+    if params:
+        tree["model"].setdefault("params", {}).update(params)
     if os.environ.get("CTRLORA_FAST_INIT", "1") == "0":
         net = instantiate_from_config(tree["model"])
     else:
         with skip_default_init():
             net = instantiate_from_config(tree["model"])
         fill_default_init(net, seed=int(torch.initial_seed() % (1 << 30)))
+    if getattr(net, "use_ema", False):
+        net.reseed_ema()        # the shadows were cloned while the model was built: start them at the weights it came out with
     print(f"[cldm.model] built {type(net).__name__} from {config_path}")
     return net.cpu()

@@ -360,6 +360,8 @@ int cl_adamw_dev(float* p, const float* g, float* m, float* v, long n, const flo
 long cl_grad_norm_scratch_floats(int nbuf) { return grad_norm_scratch_floats(nbuf); }
 int cl_grad_norm(const float* const* bufs, const long* counts, int nbuf, const float* hyper, const float* max_norm, float* out, float* scratch, void* stream) { return grad_norm(bufs, counts, nbuf, hyper, max_norm, out, scratch, S(stream)); }
 int cl_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip, void* stream) { return adamw_dev_clip(p, g, m, v, n, hyper, step, clip, S(stream)); }
+int cl_ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, void* stream) { return ema_update(shadow, p, n, decay, num_updates, S(stream)); }
+int cl_swap(float* a, float* b, long n, void* stream) { return swap_buffers(a, b, n, S(stream)); }
 int cl_ddim_set_t(const long* table, const int* cursor, int S_, long* ts, int n, void* stream) { return ddim_set_t(table, cursor, S_, ts, n, S(stream)); }
 int cl_ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef, const int* cursor, int S_, float scale, float* x_prev, float* pred_x0, long n, void* stream) { return ddim_step_dev(x, e_c, e_u, noise, coef, cursor, S_, scale, x_prev, pred_x0, n, S(stream)); }
 int cl_timestep_embedding_f(int dtype, const float* t, const float* freqs, void* out, long ldo, int B, int half, void* stream) { return timestep_embed_f(dtype, t, freqs, out, ldo, B, half, S(stream)); }

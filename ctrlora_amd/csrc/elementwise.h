@@ -10,14 +10,14 @@ namespace cl {
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
 // transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
 // qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel; grad_norm: the partial
-// launch's grid, aux = buffers.
+// launch's grid, aux = buffers; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
   EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
   EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV,
-  EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP
+  EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP
 };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
@@ -67,6 +67,10 @@ int grad_norm(const float* const* bufs, const long* counts, int nbuf, const floa
               float* scratch, hipStream_t st);
 int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
                    hipStream_t st);
+// LitEma.forward over one flat fp32 buffer with device-resident decay and update count; exchange of two flat fp32 buffers
+// (elementwise.hip)
+int ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, hipStream_t st);
+int swap_buffers(float* a, float* b, long n, hipStream_t st);
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st);
 int ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                   const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, hipStream_t st);

@@ -554,6 +554,66 @@ __global__ void adamw_dev_clip_kernel(float* __restrict__ p, const float* __rest
   }
 }
 
+// ---------------------------------------------------------------- EMA of the trained weights (ldm/modules/ema.py: LitEma.forward)
+// shadow -= (1 - d) * (shadow - p) over one flat fp32 buffer, d = min(*decay, (1 + u) / (10 + u)) with u = *num_updates already
+// advanced by tick_kernel, or *decay itself for u < 0 (LitEma without the warm-up).  Decay and count are read from device memory:
+// a replayed graph follows them.  Every fp32 operation is rounded once and none is contracted, so the bits are those of torch's
+// s.sub_(omd * (s - p)) on the CPU; min() is Python's (the warm-up term wins only where it is smaller, a NaN decay stays).
+// W = 4: shadow and p share their offset from a 16-byte boundary -- 16-byte accesses from that boundary on, the elements before
+// it (head) and the last n % 4 (tail) one by one by the first threads of the grid, as zero_kernel does.  W = 1: plain grid stride.
+__device__ __forceinline__ float ema_one_minus_decay(const float* __restrict__ decay, const int* __restrict__ num_updates) {
+#pragma clang fp contract(off)
+  const int u = *num_updates;
+  float d = *decay;
+  if (u >= 0) {
+    const float w = (float)(1 + u) / (float)(10 + u);      // IEEE division: hipcc's default for fp32
+    d = w < d ? w : d;
+  }
+  return 1.0f - d;
+}
+__device__ __forceinline__ float ema_elem(float s, float p, float omd) {
+#pragma clang fp contract(off)
+  const float diff = s - p;
+  const float step = omd * diff;
+  return s - step;
+}
+template <int W>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ shadow, const float* __restrict__ p, long head,
+                                                         long nvec, long tail, const float* __restrict__ decay,
+                                                         const int* __restrict__ num_updates) {
+#pragma clang fp contract(off)
+  const float omd = ema_one_minus_decay(decay, num_updates);
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  if constexpr (W == 4) {
+    float4* __restrict__ sb = reinterpret_cast<float4*>(shadow + head);
+    const float4* __restrict__ pb = reinterpret_cast<const float4*>(p + head);
+    for (long i = i0; i < nvec; i += stride) {
+      float4 s = sb[i];
+      const float4 q = pb[i];
+      s.x = ema_elem(s.x, q.x, omd); s.y = ema_elem(s.y, q.y, omd); s.z = ema_elem(s.z, q.z, omd); s.w = ema_elem(s.w, q.w, omd);
+      sb[i] = s;
+    }
+    if (i0 < head) shadow[i0] = ema_elem(shadow[i0], p[i0], omd);
+    if (i0 < tail) { const long e = head + (nvec << 2) + i0; shadow[e] = ema_elem(shadow[e], p[e], omd); }
+  } else {
+    for (long i = i0; i < nvec; i += stride) shadow[i] = ema_elem(shadow[i], p[i], omd);
+  }
+}
+// a <-> b over two disjoint fp32 buffers, the same two forms (ema_scope: shadow into the masters and back, no third copy)
+template <int W>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long head, long nvec, long tail) {
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  if constexpr (W == 4) {
+    float4* __restrict__ av = reinterpret_cast<float4*>(a + head);
+    float4* __restrict__ bv = reinterpret_cast<float4*>(b + head);
+    for (long i = i0; i < nvec; i += stride) { const float4 x = av[i], y = bv[i]; av[i] = y; bv[i] = x; }
+    if (i0 < head) { const float x = a[i0]; a[i0] = b[i0]; b[i0] = x; }
+    if (i0 < tail) { const long e = head + (nvec << 2) + i0; const float x = a[e]; a[e] = b[e]; b[e] = x; }
+  } else {
+    for (long i = i0; i < nvec; i += stride) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
+  }
+}
+
 // DDIM loop with a device cursor i = 0..S-1 (ddim_hacked.py:157-160): index = S-1-i, ts = ddim_timesteps[index]
 __global__ void ddim_set_t_kernel(const long* __restrict__ table, const int* __restrict__ cursor, int S,
                                   long* __restrict__ ts, int n) {
@@ -1212,6 +1272,40 @@ int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const f
   const dim3 grid(ew_grid(n));
   hipLaunchKernelGGL(adamw_dev_clip_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step, clip);
   return ew_done(EW_ADAMW_DEV_CLIP, -1, grid, 256);
+}
+// The two-buffer streaming launches: form 1 = 16-byte accesses (both buffers the same distance from a 16-byte boundary) with a
+// scalar head and tail, form 0 = one element per work item; aux = the 16-byte vectors.
+struct PairSplit { bool vec; long head, nvec, tail; };
+static inline PairSplit pair_split(const float* a, const float* b, long n) {
+  const uintptr_t oa = reinterpret_cast<uintptr_t>(a) & 15, ob = reinterpret_cast<uintptr_t>(b) & 15;
+  if (oa != ob) return {false, 0, n, 0};
+  long head = (long)(((16 - oa) & 15) >> 2);
+  if (head > n) head = n;
+  const long nvec = (n - head) >> 2;
+  return {true, head, nvec, n - head - (nvec << 2)};
+}
+static inline bool mis4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
+int ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, hipStream_t st) {
+  ew_rec_begin();
+  if (n < 0 || !decay || !num_updates || (n > 0 && (!shadow || !p))) return CL_EINVAL;
+  if (n == 0) return CL_OK;
+  if (mis4(shadow) || mis4(p) || overlaps(shadow, n, p, n)) return CL_EINVAL;
+  const PairSplit s = pair_split(shadow, p, n);
+  const dim3 grid(ew_grid(s.nvec));
+  if (s.vec) hipLaunchKernelGGL((ema_update_kernel<4>), grid, dim3(256), 0, st, shadow, p, s.head, s.nvec, s.tail, decay, num_updates);
+  else hipLaunchKernelGGL((ema_update_kernel<1>), grid, dim3(256), 0, st, shadow, p, 0L, n, 0L, decay, num_updates);
+  return ew_done(EW_EMA_UPDATE, -1, grid, 256, s.vec ? 1 : 0, s.vec ? s.nvec : 0);
+}
+int swap_buffers(float* a, float* b, long n, hipStream_t st) {
+  ew_rec_begin();
+  if (n < 0 || (n > 0 && (!a || !b))) return CL_EINVAL;
+  if (n == 0 || a == b) return CL_OK;
+  if (mis4(a) || mis4(b) || overlaps(a, n, b, n)) return CL_EINVAL;
+  const PairSplit s = pair_split(a, b, n);
+  const dim3 grid(ew_grid(s.nvec));
+  if (s.vec) hipLaunchKernelGGL((swap_kernel<4>), grid, dim3(256), 0, st, a, b, s.head, s.nvec, s.tail);
+  else hipLaunchKernelGGL((swap_kernel<1>), grid, dim3(256), 0, st, a, b, 0L, n, 0L);
+  return ew_done(EW_SWAP, -1, grid, 256, s.vec ? 1 : 0, s.vec ? s.nvec : 0);
 }
 int ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, hipStream_t st) {
   ew_rec_begin();

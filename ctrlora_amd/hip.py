@@ -129,6 +129,8 @@ _SIGS = {
     "cl_grad_norm_scratch_floats": [_I],
     "cl_grad_norm": [_P, _P, _I, _P, _P, _P, _P, _P],
     "cl_adamw_dev_clip": [_P, _P, _P, _P, _L, _P, _P, _P, _P],
+    "cl_ema_update": [_P, _P, _L, _P, _P, _P],
+    "cl_swap": [_P, _P, _L, _P],
 }
 _LONG_RESULT = ("cl_groupnorm_ws_floats", "cl_grad_norm_scratch_floats")
 EXPORTED = tuple(_SIGS.keys())
@@ -841,6 +843,21 @@ def adamw_dev_clip(p, g, m, v, hyper, step, clip):
     """adamw_dev on g * (grad_scale * clip[1]); clip = grad_norm's out.  clip[1] == 1 gives adamw_dev's bits."""
     _chk(lib().cl_adamw_dev_clip(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(),
                                  step.data_ptr(), clip.data_ptr(), stream()), "cl_adamw_dev_clip")
+
+
+def ema_update(shadow, p, decay, num_updates):
+    """LitEma.forward over one flat fp32 buffer: shadow -= (1 - d) * (shadow - p), d from the device scalars `decay` (fp32) and
+    `num_updates` (int32, advanced with tick() ONCE per optimizer step, before the first bank; negative = no warm-up)."""
+    assert shadow.dtype == p.dtype == decay.dtype == torch.float32 and num_updates.dtype == torch.int32
+    assert shadow.is_contiguous() and p.is_contiguous() and shadow.numel() == p.numel(), (shadow.shape, p.shape)
+    _chk(lib().cl_ema_update(shadow.data_ptr(), p.data_ptr(), p.numel(), decay.data_ptr(), num_updates.data_ptr(), stream()),
+         "cl_ema_update")
+
+
+def swap_(a, b):
+    """Exchange the contents of two contiguous fp32 tensors in place (one launch, no third buffer)."""
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    _chk(lib().cl_swap(a.data_ptr(), b.data_ptr(), a.numel(), stream()), "cl_swap")
 
 
 def ddim_set_t(table, cursor, S, ts):

@@ -6,7 +6,8 @@
   * PLossFn        -- p_losses' reduction {loss_simple, loss_vlb, loss} + d loss / d eps, one deterministic kernel pair
                       (ddpm.py:902-918 with logvar = 0).
   * FusedAdamW     -- torch.optim.AdamW semantics (cldm_ctrlora_finetune.py:105) as ONE kernel over the
-                      flat master/grad buffers, followed by the re-pack of the trainables.
+                      flat master/grad buffers, followed by the re-pack of the trainables; with `attach_ema()` the EMA of
+                      the trained weights (ldm/modules/ema.py) is one more kernel per bank inside the same step.
   * PretrainAdamW  -- the same over the base buffer and every LoRA bank that has joined (both: _FlatAdamW + _AdamState).
   * bind_trainables -- re-points the ControlNet's trainable nn.Parameters at the flat buffers.
   * GraphedTrainStep -- the optimizer step as hipGraph replays of the pieces capture_plan() lists.
@@ -267,6 +268,34 @@ class FusedAdamW(_FlatAdamW):
         super().__init__(params, dev, lr, betas, eps, weight_decay, grad_scale)
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._states = [_AdamState(ex.tr, self._step_dev, partial(_legacy_rounds_1_3, ex)) for ex in self.executors]
+        self.ema, self._ema_flats = None, None
+
+    def attach_ema(self, ema, flats):
+        """EMA of the trained weights inside the step (ldm.modules.ema.ModelEma bound to the executors; `flats`: its flat shadow
+        buffer per bank, laid out like that bank's masters).  From here on `_update()` ticks `ema.num_updates` once per optimizer
+        step and follows every bank's AdamW launch with cl_ema_update on the updated masters -- after the last accumulation
+        micro-step and after the gradient exchange, like the rest of the step, so every rank computes the same shadows and
+        nothing is exchanged.  `ema.decay` lives in device memory and follows `sync_hyper()`'s rule (ModelEma.set_decay).
+        Attaching changes what is launched: do it before a capture, not after.  Without it nothing changes."""
+        flats = list(flats)
+        assert len(flats) == len(self.executors)
+        for ex, f in zip(self.executors, flats):
+            assert f.dtype == torch.float32 and f.shape == ex.tr.flat.shape and f.device == ex.tr.flat.device
+        assert ema.decay.device == ema.num_updates.device == self._hyper.device
+        self.ema, self._ema_flats = ema, flats
+        self.sync_hyper()
+
+    def sync_hyper(self):
+        super().sync_hyper()
+        if getattr(self, "ema", None) is not None:
+            self.ema.sync()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self.ema is not None and self.ema.in_scope:
+            raise RuntimeError("opt.step() inside ema_scope(): the masters hold the EMA weights, a step would train the average "
+                               "and average the result; leave the scope first")
+        return super().step(closure)
 
     _step = property(lambda self: int(self._step_dev.item()))
     _m = property(lambda self: [st.m for st in self._states])
@@ -275,11 +304,16 @@ class FusedAdamW(_FlatAdamW):
     def _update(self):
         clip = self._grad_norm([ex.tr.flat_grad for ex in self.executors])
         hip.tick(self._step_dev)          # one tick per optimizer step, however many banks follow
-        for ex, st in zip(self.executors, self._states):
+        ema = self.ema
+        if ema is not None and ema.use_num_updates:
+            hip.tick(ema.num_updates)     # LitEma counts before it averages; without the warm-up the count stays at -1
+        for k, (ex, st) in enumerate(zip(self.executors, self._states)):
             if clip:
                 hip.adamw_dev_clip(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev, self.grad_norm_out)
             else:
                 hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
+            if ema is not None:
+                hip.ema_update(self._ema_flats[k], ex.tr.flat, ema.decay, ema.num_updates)
             ex.repack()
 
     def zero_grad(self, set_to_none: bool = False):
@@ -441,8 +475,11 @@ class GraphedTrainStep:
             from .parallel import all_reduce_slice, payload_dtype_from_env
             payload = payload_dtype_from_env()       # CTRLORA_DP_PAYLOAD=bf16: half the bytes per bucket
 
+            world = self.world               # not `self`: a closure over it would make this object a reference cycle, and
+                                             # its graphs would go only when the cycle collector runs, possibly inside a capture
+
             def reduce_fn(buf):
-                if dist.is_initialized() and self.world > 1:
+                if dist.is_initialized() and world > 1:
                     return all_reduce_slice(buf, None, payload)
                 return None
         self._reduce_fn = reduce_fn
@@ -493,6 +530,7 @@ class GraphedTrainStep:
         that warm the allocations before capture() and for batches whose shapes are not the captured ones.  Runs on this
         object's side stream, fenced against the current stream on both ends.  Returns {loss_simple, loss_vlb, loss} where the
         model has the direct path, else the loss scalar."""
+        self._refuse_in_ema_scope()
         cur = torch.cuda.current_stream()
         self._side.wait_stream(cur)
         with torch.cuda.stream(self._side):
@@ -539,8 +577,12 @@ class GraphedTrainStep:
         """Capture forward + backward as consecutive graphs that end where a gradient bucket is complete.  The
         executors' stage-completion hook (ControlNetE._done -> on_stage_done(start, end), called after the stage's last
         kernel was enqueued) closes the running capture and opens the next one in the same memory pool."""
+        import gc
         execs = list(self.opt.executors)
         saved_hooks = [ex.on_stage_done for ex in execs]
+        # what `torch.cuda.graph` does on entry, which this path does not go through: a collection DURING the capture that
+        # reached an unreferenced graph, stream or pool block would destroy it from the capturing thread, which a capture forbids
+        gc.collect()
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
         state = {"g": None, "lo": {id(ex): 0 for ex in execs}, "hi": {id(ex): 0 for ex in execs}}
@@ -595,6 +637,13 @@ class GraphedTrainStep:
             for ex, h in zip(execs, saved_hooks):
                 ex.on_stage_done = h
 
+    def _refuse_in_ema_scope(self):
+        """A replay does not pass through opt.step(): the same refusal, before anything is enqueued."""
+        ema = getattr(self.opt, "ema", None)
+        if ema is not None and ema.in_scope:
+            raise RuntimeError("a training step inside ema_scope(): the masters hold the EMA weights, a step would train the "
+                               "average and average the result; leave the scope first")
+
     def matches(self, z, cond_txt, hint, t, noise) -> bool:
         """Do these tensors have the shapes and dtypes the graphs were captured on?"""
         return self._static.matches(z, cond_txt, hint, t, noise)
@@ -608,6 +657,7 @@ class GraphedTrainStep:
         `first`: clear the gradients before; `last`: exchange the gradient buckets between the segments and run the optimizer
         piece after.  Without accumulate=True there is one form only, the whole optimizer step."""
         assert self.accumulate or (first and last), "captured as one optimizer step per replay: build with accumulate=True"
+        self._refuse_in_ema_scope()
         self._static.load(z, cond_txt, hint, t, noise)
         if first and self.g_z is not None:
             self.g_z.replay()

@@ -188,6 +188,9 @@ class Trainer:
             return self._fit_graphed(model, train_dataloader)
         acc = self.accumulate_grad_batches
         dp = getattr(model, "dp", None)
+        # an EMA of the trained weights (model.model_ema: ldm.modules.ema.ModelEma) that the optimizer does not carry inside its
+        # own step (a CPU run, a plain torch optimizer) is updated here, by the module's host restatement
+        ema_on_host = getattr(model, "model_ema", None) is not None and getattr(self.optimizer, "ema", None) is None
         self.optimizer.zero_grad()
         micro = 0
         while self.global_step < self.max_steps:
@@ -206,6 +209,8 @@ class Trainer:
                 if last:
                     norm = self._clip_torch() if self._norm_on and not self._norm_in_opt else None
                     self.optimizer.step()
+                    if ema_on_host:
+                        model.model_ema(model)      # once per optimizer step, like the engine optimizer's own update
                     if self._norm_in_opt:
                         norm = self.optimizer.last_grad_norm()[0]
                     self.optimizer.zero_grad()

@@ -493,6 +493,22 @@ int cl_grad_norm(const float* const* bufs, const long* counts, int nbuf, const f
                  float* scratch, void* stream);
 int cl_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
                       void* stream);
+/* Exponential moving average of trained weights on the device, added in ABI 7 (compatible): LitEma.forward
+ * (ldm/modules/ema.py) for one flat fp32 buffer, with no host round trip, so that it replays inside a hipGraph.
+ *   u = *num_updates (already advanced by cl_tick, like cl_adamw_dev's step)
+ *   d = u >= 0 ? min(*decay, (float)(1 + u) / (float)(10 + u)) : *decay       -- u < 0: LitEma without the warm-up
+ *   omd = 1.0f - d;   shadow[i] = shadow[i] - omd * (shadow[i] - p[i])
+ * all in fp32, every operation rounded once, nothing contracted: the bits of torch's s.sub_(omd * (s - p)) on the CPU.  min is
+ * Python's: the warm-up term is taken only where it is smaller, a NaN decay stays.  p is only read; NaN / inf propagate; the zero
+ * padding between the tensors of a flat buffer stays zero.  Any n; pointers need 4-byte alignment only, and shadow and p may
+ * sit at different distances from a 16-byte boundary (at equal distances the launch uses 16-byte accesses).
+ * Refused, before anything is launched: n < 0, a null decay / num_updates, a null shadow / p with n > 0, a pointer that is not
+ * 4-byte aligned, shadow and p overlapping.  n == 0 is CL_OK.
+ * cl_swap exchanges two fp32 buffers in place (the EMA scope: shadow into the masters and back, no third copy, no address
+ * moves).  a == b is CL_OK and changes nothing; overlapping but different a and b are refused, and so are n < 0, a null a / b
+ * with n > 0 and a pointer that is not 4-byte aligned. */
+int cl_ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, void* stream);
+int cl_swap(float* a, float* b, long n, void* stream);
 int cl_ddim_set_t(const long* table, const int* cursor, int S, long* ts, int n, void* stream);
 int cl_ddim_step_dev(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coef,
                      const int* cursor, int S, float scale, float* x_prev, float* pred_x0, long n, void* stream);

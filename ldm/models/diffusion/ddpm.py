@@ -8,6 +8,7 @@ ldm/models/diffusion/ddpm.py that the CtrLoRA hot path touches):
 Schedule buffers are computed exactly as the reference does (fp64 numpy -> fp32) so timestep / index
 bookkeeping is bit-exact; q_sample and the MSE loss run as HIP kernels when the latents are on the GPU.
 """
+import contextlib
 from functools import partial
 
 import numpy as np
@@ -56,14 +57,20 @@ class DDPM(_LightningFree):
                  cosine_s=8e-3, given_betas=None, original_elbo_weight=0., v_posterior=0., l_simple_weight=1.,
                  conditioning_key=None, parameterization="eps", scheduler_config=None, use_positional_encodings=False,
                  learn_logvar=False, logvar_init=0., make_it_fit=False, ucg_training=None, reset_ema=False,
-                 reset_num_ema_updates=False):
+                 reset_num_ema_updates=False, ema_decay=0.9999):
         super().__init__()
-        if parameterization != "eps" or use_ema or learn_logvar:
-            raise NotImplementedError("CtrLoRA configs: eps-parameterisation, use_ema=False, fixed logvar")
+        if parameterization != "eps" or learn_logvar:
+            raise NotImplementedError("CtrLoRA configs: eps-parameterisation, fixed logvar")
+        if use_ema and not self.supports_ema:
+            raise NotImplementedError(f"use_ema=True: the EMA of the trained weights is built for fine-tuning only "
+                                      f"(ControlFinetuneLDM), not for {type(self).__name__}")
+        if not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"ema_decay={ema_decay!r} must lie in [0, 1]")
         self.parameterization, self.clip_denoised, self.log_every_t = parameterization, clip_denoised, log_every_t
         self.first_stage_key, self.image_size, self.channels = first_stage_key, image_size, channels
         self.model = DiffusionWrapper(unet_config, conditioning_key)
-        self.use_ema, self.use_scheduler = False, scheduler_config is not None
+        # use_ema: the subclass that supports it builds `self.model_ema` (ldm.modules.ema.ModelEma) once what it trains exists
+        self.use_ema, self.ema_decay, self.use_scheduler = bool(use_ema), float(ema_decay), scheduler_config is not None
         self.v_posterior, self.original_elbo_weight, self.l_simple_weight = v_posterior, original_elbo_weight, l_simple_weight
         self.monitor = monitor
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
@@ -124,6 +131,24 @@ class DDPM(_LightningFree):
         loss, loss_dict = self.shared_step(batch)
         self.log_dict(loss_dict)
         return loss
+
+    supports_ema = False      # ControlFinetuneLDM: True
+
+    @contextlib.contextmanager
+    def ema_scope(self, context=None):
+        """Run the body on the EMA weights (ddpm.py:194-207 of the reference); without use_ema a no-op, as there."""
+        if not self.use_ema:
+            yield None
+            return
+        self._ema_enter()
+        if context is not None:
+            print(f"{context}: Switched to EMA weights")
+        try:
+            yield None
+        finally:
+            self._ema_exit()
+            if context is not None:
+                print(f"{context}: Restored training weights")
 
 
 class LatentDiffusion(DDPM):

@@ -42,7 +42,21 @@ def get_parser():
     p.add_argument("--init_strength", type=float, default=1.0,
                    help="below 1: img2img from the dataset's target image -- it is noised to step int(init_strength * ddim_steps) "
                         "of the schedule and the remaining steps run from there (--sampler ddim only); 1.0: sample from noise")
+    p.add_argument("--use_ema", action="store_true", default=False,
+                   help="sample from the EMA weights: needs a config with use_ema: true and a checkpoint that carries the "
+                        "model_ema.* shadows (trained with --ema_decay)")
     return p
+
+
+def ema_refusal(model, state_dict):
+    """Why --use_ema cannot run this model / checkpoint, in one line, or None."""
+    if not getattr(model, "use_ema", False):
+        return "--use_ema: the config does not set use_ema: true, so the model keeps no EMA weights"
+    missing = [k for k in model.state_dict() if k.startswith("model_ema.") and k not in state_dict]
+    if missing:
+        return (f"--use_ema: the checkpoint lacks {len(missing)} model_ema.* tensors, e.g. '{missing[0]}' (not trained with "
+                "--ema_decay?)")
+    return None
 
 
 def target_size(h: int, w: int, resolution: int = 512):
@@ -127,13 +141,20 @@ def main(argv=None):
     pre = isinstance(model, ControlPretrainLDM)
     if pre:                                        # the checkpoint was saved with a task bank aliased into the tree
         model.control_model.switch_lora(args.task)
-    model.load_state_dict(load_state_dict(args.ckpt, location="cpu"), strict=True)
+    state = load_state_dict(args.ckpt, location="cpu")
+    if args.use_ema:
+        why = ema_refusal(model, state)
+        if why is not None:
+            raise SystemExit(why)
+    model.load_state_dict(state, strict=True)
     if pre:
         model.control_model.switch_lora(args.task)
     model = model.cuda().eval()
     print(f"Successfully load model ckpt from {args.ckpt}")
     os.makedirs(args.save_dir, exist_ok=True)
-    sample_dataset(model, make_sampler(model, args.sampler), dataset, args)
+    import contextlib
+    with (model.ema_scope("sample") if args.use_ema else contextlib.nullcontext()):
+        sample_dataset(model, make_sampler(model, args.sampler), dataset, args)
     print("Done")
 
 

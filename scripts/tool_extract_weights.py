@@ -21,9 +21,30 @@ import torch  # noqa: E402
 LORA_FILE_MARKERS = ("lora_layer", "zero_convs", "middle_block_out", "norm")
 
 
+EMA_PREFIX = "model_ema."
+
+
 def _in_control_tree(key: str) -> bool:
-    # task banks (`loras_dict.<task>.<i>`) are reached through the tree after switch_lora, never saved as such
-    return "control_model" in key and "loras_dict" not in key
+    # task banks (`loras_dict.<task>.<i>`) are reached through the tree after switch_lora, never saved as such; the EMA shadows
+    # (`model_ema.control_model...`, dots removed: ldm/modules/ema.py) name the same layers and are no part of either file
+    return "control_model" in key and "loras_dict" not in key and not key.startswith(EMA_PREFIX)
+
+
+def ema_key(key: str) -> str:
+    """Where a checkpoint trained with use_ema keeps the average of tensor `key`."""
+    return EMA_PREFIX + key.replace(".", "")
+
+
+def with_ema_values(selected: dict, ckpt: dict) -> dict:
+    """--ema: the selected keys, each with the value of its shadow -- an ordinary LoRA / control file of the averaged weights.
+    A tensor without a shadow is an error, not a silent mix of averaged and raw weights."""
+    out = {}
+    for k in selected:
+        if ema_key(k) not in ckpt:
+            raise KeyError(f"--ema: the checkpoint has no '{ema_key(k)}' (the shadow of '{k}'): it was not trained with "
+                           "--ema_decay, or trained with another set of trainable layers")
+        out[k] = ckpt[ema_key(k)].detach().clone().reshape(selected[k].shape)
+    return out
 
 
 def extract_lora(ckpt: dict) -> dict:
@@ -56,18 +77,30 @@ def get_parser():
     p.add_argument("--save_path", type=str, required=True, help="path to save extracted weights")
     p.add_argument("--from_base", action="store_true", help="extract weights from the Base ControlNet")
     p.add_argument("--from_base_config", type=str, help="path to Base ControlNet config file")
+    p.add_argument("--ema", action="store_true", help="write the EMA of every extracted tensor (the model_ema.* entries of a "
+                   "checkpoint trained with --ema_decay) under the tensor's ordinary name")
     return p
 
 
 def main(argv=None):
     from cldm.model import create_model, load_state_dict
     args = get_parser().parse_args(argv)
+    if args.ema and args.from_base:
+        raise SystemExit("--ema cannot be combined with --from_base: pre-training keeps no EMA")
     ckpt = load_state_dict(args.ckpt, location="cpu")
+
+    def averaged(selected):          # --ema: the shadows' values under the selected names
+        if not args.ema:
+            return selected
+        try:
+            return with_ema_values(selected, ckpt)
+        except KeyError as e:
+            raise SystemExit(e.args[0])
     if args.type == "control":
-        torch.save(extract_control(ckpt), args.save_path)
+        torch.save(averaged(extract_control(ckpt)), args.save_path)
         print(f"Extracted weights saved to {args.save_path}")
     elif not args.from_base:
-        torch.save(extract_lora(ckpt), args.save_path)
+        torch.save(averaged(extract_lora(ckpt)), args.save_path)
         print(f"Extracted weights saved to {args.save_path}")
     else:
         assert not os.path.isfile(args.save_path)

@@ -58,7 +58,23 @@ def get_parser():
                         "inside the step (Trainer(gradient_clip_val=)); 0 = off (the default)")
     p.add_argument("--track_grad_norm", action="store_true", default=False,
                    help="log the global L2 norm of the gradients as train/grad_norm without clipping (off by default)")
+    p.add_argument("--ema_decay", type=_ema_decay, default=0.0,
+                   help="keep an exponential moving average of the trained weights with this decay (LitEma's rule, warm-up "
+                        "included; 0.9999 is its default), updated on the device inside every optimizer step and saved in the "
+                        "checkpoints as model_ema.*; extract it with tool_extract_weights.py --ema; 0 = off (the default)")
     return p
+
+
+def _ema_decay(text):
+    value = float(text)
+    if not 0.0 <= value <= 1.0:
+        raise argparse.ArgumentTypeError(f"--ema_decay {text}: a decay lies in [0, 1] (0 = off)")
+    return value
+
+
+def ema_model_params(ema_decay: float) -> dict:
+    """--ema_decay F with F in (0, 1]: what create_model overrides in the config's model.params; nothing for 0."""
+    return dict(use_ema=True, ema_decay=float(ema_decay)) if ema_decay > 0.0 else {}
 
 
 def init_weights(model, sd_weights: dict, control_weights: dict, report_dir: str = "./tmp"):
@@ -78,6 +94,8 @@ def init_weights(model, sd_weights: dict, control_weights: dict, report_dir: str
     for k in copied_cn:
         scratch[k] = control_weights[k].clone()
     model.load_state_dict(scratch, strict=True)
+    if getattr(model, "use_ema", False):
+        model.reseed_ema()      # `scratch` carried the construction-time shadows along: the average starts at the loaded weights
     if report_dir:
         os.makedirs(report_dir, exist_ok=True)
         for name, keys in (("finetune_missing_keys_sd", missing_sd), ("finetune_copied_keys_sd", copied_sd),
@@ -126,7 +144,7 @@ def main(argv=None):
         print("Batch size per device:", args.bs)
         print("Gradient accumulation:", args.gradacc)
         print("Total batch size:", args.bs * world * args.gradacc)
-    model = create_model(args.config).cpu()
+    model = create_model(args.config, params=ema_model_params(args.ema_decay)).cpu()
     model.learning_rate = args.lr
     model.sd_locked = True
     model.only_mid_control = False
