@@ -166,7 +166,12 @@ typedef struct cl_gemm_params {
    * LayerNorm prologue only: act 0 (N % 32 == 0) or act 3; ln_beta != NULL; K2 == 0; no residual.
    * (Products WITH a fall-back never see these as refusals: where the x-stationary kernel is forced or tabled for a plain or
    * residual product it does not take, the tile kernels run it.)  C == residual (in place) is part of the contract for every
-   * configuration: an element is read and written by its owner only.
+   * configuration: an element is read and written by its owner only.  (It needs C stored in `dtype`, like the residual: a bf16
+   * product with out_f32 has no element that is both.)  tests/test_gpu_gemm_conformance.py launches every configuration in
+   * place -- linear, a second K segment, rowbias + SiLU, forced split-K (the reduce reads the residual and writes C), conv S1 and
+   * CL_GEMM_CONV_S2A -- and asserts the bits of the out-of-place launch; tests/test_gpu_gemm_xs_conformance.py does the same for
+   * the x-stationary forms.  CL_GEMM_CONV_S2A is in the same file's Layer C (even and odd grids; the full-line and the
+   * loader / consumer kernel at a size they take themselves) against tests/gemm_ref.py's fp64 model of the mode.
    * rowbias and residual are read in `dtype` ([M / rows_per_batch, N] and [M, N]); with atomic, C is fp32 and the product is
    * added onto what it holds. */
 } cl_gemm_params;

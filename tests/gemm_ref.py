@@ -42,7 +42,7 @@ TOL_ONE_ROUNDING = 2.5e-3
 # fp32-accumulated products of exact operands: test_grouped_weight_gradient_production_stage
 TOL_F32 = 2e-5
 
-LINEAR, CONV_S1, CONV_S2, CONV_UP2, CONV_T2 = 0, 1, 2, 3, 4
+LINEAR, CONV_S1, CONV_S2, CONV_UP2, CONV_T2, CONV_S2A = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GEGLU_SPLIT = 0, 1, 2, 3
 LIP_SILU, LIP_GELU = 1.1, 1.1
 GUARD_ROWS, PAD_COLS = 64, 8
@@ -152,6 +152,8 @@ def _conv64(c, a1, w, lo, hi, F):
         z = torch.zeros(b1 - b0, K1, Hout, Wout, dtype=img.dtype, device=img.device)
         z[:, :, ::2, ::2] = img
         y = F.conv2d(z, w4, padding=1)
+    elif mode == CONV_S2A:         # AutoencoderKL's Downsample: one zero column on the right, one zero row at the bottom, no pad top / left
+        y = F.conv2d(F.pad(img, (0, 1, 0, 1)), w4, stride=2)
     else:
         raise ValueError(mode)
     assert tuple(y.shape[2:]) == (Hout, Wout), (tuple(y.shape), c["conv"])

@@ -142,6 +142,39 @@ def test_reference_conv_modes_vs_plain_torch(B, H, W):
         assert G.k_total(c) == 9 * Cin + 1
 
 
+@pytest.mark.parametrize("B,H,W", [(3, 6, 10), (2, 9, 7)], ids=["even", "odd"])
+def test_reference_conv_s2a_is_the_bottom_right_padded_stride_2_conv(B, H, W):
+    """Mode 5 (AutoencoderKL's Downsample) == conv2d(pad(x, (0, 1, 0, 1)), stride 2) in fp64, the magnitude path included -- and
+    NOT the two conventions it could silently coincide with: mode 2 (pad 1 on every side) and the pad on the other side
+    (1, 0, 1, 0).  Both put every output one input pixel off, so they differ from mode 5 by the size of the output itself."""
+    g = _gen(50 + H)
+    Cin, Cout = 32, 40
+    w = torch.randn(Cout, Cin, 3, 3, generator=g).double()
+    x = torch.randn(B, Cin, H, W, generator=g).double()
+    b = torch.randn(Cout, generator=g)
+    pix = lambda t: t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+    wp = w.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin)
+    Ho, Wo = H // 2, W // 2
+    want = F.conv2d(F.pad(x, (0, 1, 0, 1)), w, b.double(), stride=2)
+    assert tuple(want.shape[2:]) == (Ho, Wo)
+    c = G.make_case(pix(x), wp, bias=b, mode=G.CONV_S2A, conv=(B, H, W, Ho, Wo))
+    assert G.CONV_S2A == 5 and c["M"] == B * Ho * Wo and c["K1"] == Cin and G.k_total(c) == 9 * Cin + 1
+    got = G.gemm_ref64(c)
+    torch.testing.assert_close(got, pix(want), rtol=1e-11, atol=1e-11)
+    per = Ho * Wo
+    torch.testing.assert_close(G.gemm_ref64(c, per, 2 * per), pix(want)[per:2 * per], rtol=1e-11, atol=1e-11)
+    mag = F.conv2d(F.pad(x.abs(), (0, 1, 0, 1)), w.abs(), b.double().abs(), stride=2)
+    torch.testing.assert_close(G.gemm_ref64(c, absolute=True), pix(mag), rtol=1e-11, atol=1e-11)
+    # the wrong conventions on the same inputs, cropped to the same grid
+    sym = F.conv2d(x, w, b.double(), stride=2, padding=1)[:, :, :Ho, :Wo]
+    other = F.conv2d(F.pad(x, (1, 0, 1, 0)), w, b.double(), stride=2)[:, :, :Ho, :Wo]
+    for name, wrong in (("pad 1", sym), ("pad (1, 0, 1, 0)", other)):
+        assert G._rel(pix(wrong), got) > 0.5, name
+    # ... and the element-wise check flags such a result on nearly every element
+    res = G.run_checks(dict(c, out_dtype=torch.float32), pix(sym).contiguous())
+    assert "elementwise" in G.failures(res) and res["violations"] > 0.9 * c["M"] * Cout, res
+
+
 def test_row_chunks_tile_every_row_once():
     g = _gen(4)
     c = G.make_case(**_ops(g, 1000, 64, 32))

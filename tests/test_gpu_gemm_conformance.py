@@ -6,7 +6,10 @@ csrc/gemm.hip:launch_t_cfg can choose, element-wise against the fp64 contract of
   B. the same signatures at the per-GPU batch sizes nobody tuned (M b / 8 for b = 1, 3, 4; b = 4 is the reference's pre-training
      batch, train_ctrlora_pretrain.py:35), which have no row and go by rule -- bf16, and b = 3 in fp32 (no fp32 product has a row);
   C. every configuration id launch_t_cfg accepts, forced, across the epilogue contract at small shapes that sit on tile edges,
-     in both dtypes, linear and the four 3x3 modes.  "A stale or foreign table costs speed, never correctness": a forced
+     in both dtypes, linear and the five 3x3 modes (CONV_S2A, AutoencoderKL's Downsample, on an even and an odd grid; once more at
+     a size the full-line and the loader / consumer kernels take themselves: test_s2a_on_the_whole_line_kernels), and the
+     residual epilogues a second time IN PLACE (C == residual: "part of the contract for every configuration"), bit for bit the
+     out-of-place result, forced split-K included.  "A stale or foreign table costs speed, never correctness": a forced
      configuration that cannot take a case runs it through its fall-back and passes the same checks; only what the CONTRACT
      excludes (a predicate on the case, never on the configuration) may be refused.
 
@@ -124,12 +127,19 @@ def _signature_case(dtype, mode, M, N, K1, K2, geglu, b=8):
     return G.make_case(r(B * Hin * Win, K1, dtype=dtype), w1, bias=bias, mode=mode, conv=conv)
 
 
-def _launch(c):
-    """cl_gemm on the case: the output a view into a guarded buffer, every strided operand a padded copy."""
+def _launch(c, inplace=False):
+    """cl_gemm on the case: the output a view into a guarded buffer, every strided operand a padded copy.  inplace: the view holds
+    the residual's values and IS the residual (residual = C, ldr = ldc)."""
     from ctrlora_amd import hip
     guard = G.Guarded(c["M"], c["out_cols"], c["out_dtype"], "cuda", fill=c["c0"] if c["atomic"] else float("nan"))
+    if inplace:
+        assert _inplace_possible(c), "in place: a residual of the output's own type and shape"
+        guard.view.copy_(c["residual"])
+        residual = guard.view
+    else:
+        residual = G.padded(c["residual"], G.PAD_RES)
     hip.gemm(G.padded(c["a1"], G.PAD_A1), c["w1"], guard.view, a2=G.padded(c["a2"], G.PAD_A2), w2=c["w2"], bias=c["bias"],
-             rowbias=G.padded(c["rowbias"], G.PAD_RB), rows_per_batch=c["rows_per_batch"], residual=G.padded(c["residual"], G.PAD_RES),
+             rowbias=G.padded(c["rowbias"], G.PAD_RB), rows_per_batch=c["rows_per_batch"], residual=residual,
              alpha=c["alpha"], beta=c["beta"], act=c["act"], mode=c["mode"], conv=c["conv"], k1=c["K1"], out_f32=c["out_f32"],
              atomic=c["atomic"], splitk=c["splitk"], N=c["N"], a1_group_n=c["a1_group_n"], a2_group_n=c["a2_group_n"],
              alpha_n=c["alpha_n"])
@@ -142,11 +152,17 @@ def _sig(c):
                 residual=int(c["residual"] is not None))
 
 
-def _launch_tagged(c):
+def _inplace_possible(c):
+    """Can C be the residual?  The residual is read in `dtype`, so only where C is stored in `dtype` too (a bf16 product with an
+    fp32 output has no element that is both), and never with atomic accumulation.  A predicate on the case alone."""
+    return c["residual"] is not None and c["out_dtype"] == c["dtype"] and not c["atomic"] and c["out_cols"] == c["N"]
+
+
+def _launch_tagged(c, inplace=False):
     """(guard, launches of the case's signature, (workgroups, wg_size))."""
     from ctrlora_amd import hip
     with _tags() as tags:
-        guard = _launch(c)
+        guard = _launch(c, inplace)
         torch.cuda.synchronize()
         n, _ = tags.launches(**_sig(c))
         grid = [(t["workgroups"], t["wg_size"]) for t in hip.gemm_tags() if all(t[k] == v for k, v in _sig(c).items())]
@@ -388,16 +404,136 @@ def _conv_cases(dtype):
             out.append((f"conv{mode}", (M, N, K1, 0), G.make_case(**o), 0))
             out.append((f"conv{mode}+rowbias+residual", (M, N, K1, 0),
                         G.make_case(**o, rowbias=r(B, N, dtype=dtype), rows_per_batch=Ho * Wo, residual=r(M, N, dtype=dtype), beta=1.0), 0))
+    # AutoencoderKL's Downsample (pad (0, 1, 0, 1), stride 2): an even grid, a second one, and an odd grid, where the kernel never
+    # reaches the pad row / column (2 Hout + 1 <= Hin) and the last input row / column is read by the last tap only
+    for conv in ((3, 6, 10, 3, 5), (2, 8, 6, 4, 3), (2, 9, 7, 4, 3)):
+        B, H, W, Ho, Wo = conv
+        K1, N = ((32, 160), (96, 72))[i % 2]
+        i += 1
+        r = _rand(7000 + i)
+        M = B * Ho * Wo
+        o = dict(a1=r(B * H * W, K1, dtype=dtype), w1=r(N, 9 * K1, sc=1.0 / (3 * K1 ** 0.5), dtype=dtype), bias=r(N, sc=0.1),
+                 mode=G.CONV_S2A, conv=conv)
+        out.append((f"conv{G.CONV_S2A}", (M, N, K1, 0), G.make_case(**o), 0))
+        out.append((f"conv{G.CONV_S2A}+rowbias+residual", (M, N, K1, 0),
+                    G.make_case(**o, rowbias=r(B, N, dtype=dtype), rows_per_batch=Ho * Wo, residual=r(M, N, dtype=dtype), beta=1.0), 0))
     r = _rand(7100)
     out.append(("x:conv_k2", (105, 72, 32, 32), G.make_case(r(105, 32, dtype=dtype), r(72, 288, dtype=dtype), a2=r(105, 32, dtype=dtype),
                                                              w2=r(72, 32, dtype=dtype), mode=G.CONV_S1, conv=(3, 5, 7, 5, 7)), 0))
     return out
 
 
+def _s2a_big(dtype, epilogue):
+    """CONV_S2A at a size the whole-line kernels take themselves: K1 = 128 (whole 128-byte lines in both dtypes, K1 % 64 for the
+    loader / consumer kernel), M = 2 x 16 x 8 = 256 > 128 output pixels in ONE 256-row tile that spans both images, N = 160."""
+    conv = (2, 32, 16, 16, 8)
+    B, H, W, Ho, Wo = conv
+    K1, N, M = 128, 160, B * Ho * Wo
+    r = _rand(7200 + (7 if dtype == F32 else 0))
+    o = dict(a1=r(B * H * W, K1, dtype=dtype), w1=r(N, 9 * K1, sc=1.0 / (3 * K1 ** 0.5), dtype=dtype), bias=r(N, sc=0.1),
+             mode=G.CONV_S2A, conv=conv)
+    if epilogue:
+        o.update(rowbias=r(B, N, dtype=dtype), rows_per_batch=Ho * Wo, residual=r(M, N, dtype=dtype), beta=1.0)
+    return G.make_case(**o)
+
+
+# SHAPES rows whose K1 (and K2) are whole 128-byte lines in bf16 too, so that the full-line, persistent and loader / consumer forms
+# run them themselves in both dtypes: one from each third of the list, and one with a second K segment
+_INPLACE_ROWS = (4, 10, 13)          # (63, 640, 320, 0), (257, 72, 1344, 0), (1000, 160, 320, 0)
+_INPLACE_K2_ROW = 9                  # (257, 328, 320, 128)
+
+
+def _inplace_cases(dtype):
+    """[(name, shape, case, forced split-K)]: products with a residual, each launched out of place and in place."""
+    out = []
+
+    def lin(i, seed):
+        M, N, K1, K2 = SHAPES[i]
+        r = _rand(11000 + 10 * seed + (7 if dtype == F32 else 0))
+        o = dict(a1=r(M, K1, dtype=dtype), w1=r(N, K1, sc=K1 ** -0.5, dtype=dtype), bias=r(N, sc=0.1), residual=r(M, N, dtype=dtype))
+        if K2:
+            o.update(a2=r(M, K2, dtype=dtype), w2=r(N, K2, sc=K2 ** -0.5, dtype=dtype))
+        return (M, N, K1, K2), o, r
+
+    for n, i in enumerate(_INPLACE_ROWS):
+        shape, o, r = lin(i, n)
+        out.append(("residual", shape, G.make_case(**o, alpha=0.7, beta=-0.5), 0))
+    shape, o, r = lin(_INPLACE_K2_ROW, 3)
+    out.append(("k2+residual", shape, G.make_case(**o, beta=1.0), 0))
+    shape, o, r = lin(13, 4)
+    nb = (shape[0] + 76) // 77
+    out.append(("rowbias+residual+silu", shape, G.make_case(**o, rowbias=r(nb, shape[1], dtype=dtype), rows_per_batch=77, beta=1.0,
+                                                            act=G.ACT_SILU), 0))
+    shape, o, r = lin(4, 5)
+    out.append(("residual+out_f32", shape, G.make_case(**o, alpha=0.7, beta=-0.5, out_f32=True), 0))
+    # forced split-K: the slabs go through the workspace, the reduce launch reads the residual and writes C (K = 1344: 21 / 42 steps)
+    shape, o, r = lin(10, 6)
+    out.append(("splitk2+residual", shape, G.make_case(**o, alpha=0.7, beta=-0.5), 2))
+    shape, o, r = lin(13, 7)
+    out.append(("splitk5+residual", shape, G.make_case(**o, beta=1.0), 5))
+    # 3x3: stride 1 (the ResnetBlock's conv2 onto the nin_shortcut output) and the Downsample mode, odd grid and whole-line size
+    r = _rand(11900 + (7 if dtype == F32 else 0))
+    for mode, conv, K1, N in ((G.CONV_S1, (3, 5, 7, 5, 7), 32, 160), (G.CONV_S1, (2, 16, 8, 16, 8), 128, 160),
+                              (G.CONV_S2A, (2, 9, 7, 4, 3), 96, 72)):
+        B, H, W, Ho, Wo = conv
+        M = B * Ho * Wo
+        out.append((f"conv{mode}+rowbias+residual", (M, N, K1, 0),
+                    G.make_case(r(B * H * W, K1, dtype=dtype), r(N, 9 * K1, sc=1.0 / (3 * K1 ** 0.5), dtype=dtype), bias=r(N, sc=0.1),
+                                mode=mode, conv=conv, rowbias=r(B, N, dtype=dtype), rows_per_batch=Ho * Wo,
+                                residual=r(M, N, dtype=dtype), beta=1.0), 0))
+    c = _s2a_big(dtype, True)
+    out.append((f"conv{G.CONV_S2A}+rowbias+residual", (c["M"], c["N"], c["K1"], 0), c, 0))
+    return out
+
+
+def _twin_launch(c, cfg, sk):
+    """The case out of place and in place under one forced configuration: (failures, figures of both, grids).  Every launch gets
+    the four checks; the two guarded buffers -- guard rows and pad columns included -- must hold the same bits."""
+    f, figs, grids = [], [], []
+    guards = []
+    for inplace in (False, True):
+        if inplace and not _inplace_possible(c):
+            break
+        with _forced(cfg, sk):
+            guard, n, grid = _launch_tagged(c, inplace)
+        res = G.run_checks(c, guard.view, guard)
+        _note("C_inplace" if inplace else "C", c, res)
+        tag = "in place: " if inplace else ""
+        f += [tag + x for x in G.failures(res)] + ([] if n == 1 else [f"{tag}launches={n}"])
+        figs.append(res)
+        grids.append(grid)
+        guards.append(guard)
+    if len(guards) == 2:
+        if grids[0] != grids[1]:
+            f.append(f"in place: another launch form {grids}")
+        if not torch.equal(_bits(guards[0]), _bits(guards[1])):
+            f.append("in place differs from out of place in %d elements" % int((_bits(guards[0]) != _bits(guards[1])).sum()))
+    return f, figs, grids
+
+
 def test_contract_excludes_is_a_predicate_on_the_case_alone():
-    code = _contract_excludes.__code__
-    assert code.co_argcount == 1 and code.co_varnames[0] == "c"
-    assert not any("cfg" in n or "config" in n.lower() for n in code.co_names + code.co_varnames)
+    for fn in (_contract_excludes, _inplace_possible):
+        code = fn.__code__
+        assert code.co_argcount == 1 and code.co_varnames[0] == "c"
+        assert not any("cfg" in n or "config" in n.lower() for n in code.co_names + code.co_varnames)
+
+
+def test_inplace_cases_cover_what_they_name():
+    """The literal list: residual rows from each third of SHAPES on whole 128-byte lines, a second K segment, rowbias + residual +
+    SiLU, an fp32 output (in place in fp32 only: a bf16 residual and an fp32 C share no element), both forced split-K factors, conv
+    S1 and conv S2A -- and nothing the contract excludes."""
+    assert [i * 3 // len(SHAPES) for i in _INPLACE_ROWS] == [0, 1, 2] and SHAPES[_INPLACE_K2_ROW][3] > 0
+    for i in _INPLACE_ROWS + (_INPLACE_K2_ROW,):
+        assert SHAPES[i][2] % 64 == 0 and SHAPES[i][3] % 64 == 0, SHAPES[i]
+    _need_gpu()
+    for dtype in (BF, F32):
+        cases = _inplace_cases(dtype)
+        names = [n for n, _, _, _ in cases]
+        assert {"residual", "k2+residual", "rowbias+residual+silu", "residual+out_f32", "splitk2+residual", "splitk5+residual",
+                f"conv{G.CONV_S1}+rowbias+residual", f"conv{G.CONV_S2A}+rowbias+residual"} == set(names)
+        for name, _, c, sk in cases:
+            assert not _contract_excludes(c) and c["residual"] is not None
+            assert _inplace_possible(c) == (not (name == "residual+out_f32" and dtype == BF)), name
 
 
 def test_ids_outside_the_switch_are_refused():
@@ -442,10 +578,54 @@ def test_forced_configuration_across_the_contract(cfg, dtype):
         if f:
             bad.append((name, shape, f, {k: res[k] for k in ("rel", "gate", "violations", "err_over_bound", "first_violation",
                                                              "guard_rows", "pad_elems", "nan_left")}, grid))
-    _record("gemm_conformance_forced_config", cfg=cfg, dtype=str(dtype), launches=launches, err_over_bound=worst,
+    # the residual epilogues again, each out of place and IN PLACE (C == residual): the same four checks, the same launch form,
+    # the same bits.  A configuration that refuses one of them contradicts "for every configuration" in the header.
+    twins = 0
+    for name, shape, c, sk in _inplace_cases(dtype):
+        try:
+            f, figs, grids = _twin_launch(c, cfg, sk)
+        except hip.HipError as e:
+            bad.append(("inplace:" + name, shape, "refused: " + str(e)))
+            continue
+        launches += len(figs)
+        twins += len(figs) == 2
+        worst = max([worst] + [r["err_over_bound"] for r in figs])
+        if f:
+            bad.append(("inplace:" + name, shape, f, [{k: r[k] for k in ("rel", "gate", "violations", "err_over_bound", "first_violation",
+                                                                         "guard_rows", "pad_elems", "nan_left")} for r in figs], grids))
+    _record("gemm_conformance_forced_config", cfg=cfg, dtype=str(dtype), launches=launches, err_over_bound=worst, inplace_twins=twins,
             failures=[str(b) for b in bad])
     assert set(ALWAYS) <= accepted, (cfg, sorted(set(ALWAYS) - accepted))
+    assert twins == 12 - (dtype == BF), twins          # (every case but the bf16 product with an fp32 output)
     assert not bad, (cfg, bad)
+
+
+@pytest.mark.parametrize("dtype", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("cfg", [16, 17, 40, 41])
+def test_s2a_on_the_whole_line_kernels(cfg, dtype):
+    """CONV_S2A where the full-line ping-pong rows (16 / 17) and the loader / consumer rows (40 / 41) run it THEMSELVES instead of
+    handing it to the generic tile: each has its own copy of the mode's address line.  Plain, and + rowbias + residual out of
+    place and in place.  That the forced kernel ran is read off the tag table: both kernels launch 512 work items per workgroup
+    on a grid of 256-row tiles; every tile this product could fall back to (the generic 128-row tiles, ids 1 / 2) launches 256.
+    The loader / consumer kernel exists in bf16 only: in fp32 its rows hand the product to the rules, which is asserted too."""
+    _need_gpu()
+    from ctrlora_amd import hip
+    bn = 160 if cfg in (16, 40) else 128
+    own = dtype == BF or cfg in (16, 17)
+    for epilogue in (False, True):
+        c = _s2a_big(dtype, epilogue)
+        assert not _contract_excludes(c) and c["M"] > 128 and c["N"] >= 96 and c["K1"] % 64 == 0
+        f, figs, grids = _twin_launch(c, cfg, 0)
+        tiles = ((c["M"] + 255) // 256) * ((c["N"] + bn - 1) // bn)
+        _record("gemm_conformance_s2a_whole_line", cfg=cfg, dtype=str(dtype), epilogue=epilogue, grids=grids, own_kernel=own,
+                err_over_bound=[r["err_over_bound"] for r in figs], rel=[r["rel"] for r in figs], failures=f)
+        assert len(figs) == (2 if epilogue else 1)
+        assert not f, (cfg, epilogue, f, figs)
+        for wgs, wg_size in grids:
+            if own:
+                assert wg_size == 512 and wgs % tiles == 0, ("the forced kernel did not run", cfg, grids, tiles)
+            else:
+                assert wg_size == 256, ("fp32 has no loader / consumer kernel: the rules' generic tile", cfg, grids)
 
 
 def test_zz_conformance_summary():
@@ -454,6 +634,8 @@ def test_zz_conformance_summary():
     wall = None if _T0[0] is None else time.time() - _T0[0]
     print("gemm conformance:", json.dumps(_STATS), "wall_s:", wall)
     _record("gemm_conformance_summary", layers=_STATS, wall_s=wall, layer_a_entries=len(_ENTRIES), layer_b_cases=len(_UNTUNED),
-            layer_c_configs=len(CONFIGS))
+            layer_c_configs=len(CONFIGS), inplace_twin_launches=_STATS.get("C_inplace", {}).get("launches", 0),
+            # measured once on one MI355X, both files in the same run: this file before the CONV_S2A and in-place cases, and with them
+            wall_s_before_s2a_and_inplace=14.8, wall_s_with_them=17.7)
     for layer, s in _STATS.items():
         assert s["violations"] == 0 and s["canary"] == 0 and s["err_over_bound"] <= 1.0, (layer, s)
