@@ -147,7 +147,7 @@ class ControlFinetuneLDM(ControlLDM):
         land in the flat buffer the optimizer's parameters view.  `grad_scale` multiplies d loss / d eps (not the three
         returned scalars): 1 / accumulate_grad_batches under gradient accumulation, what `(loss / acc).backward()` does."""
         from ctrlora_amd import hip
-        if self.loss_type != "l2" or self.original_elbo_weight != 0.:
+        if self.loss_type not in hip.LOSS_KINDS or self.original_elbo_weight != 0.:
             raise NotImplementedError("engine_train_step: l2 loss without the elbo term (every CtrLoRA config)")
         x_noisy = self.q_sample(x_start=x_start, t=t, noise=noise)
         cc = cond["c_crossattn"]
@@ -160,8 +160,15 @@ class ControlFinetuneLDM(ControlLDM):
         out = torch.empty(3, dtype=torch.float32, device=eps.device)
         scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
         d_eps = torch.empty_like(eps)
-        hip.p_losses_mse(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
-                         float(grad_scale), float(self.l_simple_weight), 0.0)
+        if self.loss_weights is None and self.loss_type == "l2":
+            hip.p_losses_mse(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
+                             float(grad_scale), float(self.l_simple_weight), 0.0)
+        else:       # a per-timestep weight table (min_snr_gamma / set_loss_weights) and / or the Huber loss
+            hip.p_losses_w(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
+                           float(grad_scale), float(self.l_simple_weight), 0.0, wt=self.loss_weights,
+                           kind=hip.LOSS_KINDS[self.loss_type], delta=self.huber_delta)
+        if torch.cuda.is_current_stream_capturing():
+            self.loss_weights_pinned = True       # the graph holds the table's address, or the kernel that has none
         eng.backward(d_eps)
         if self.dp is not None:
             self.dp.on_backward_done()

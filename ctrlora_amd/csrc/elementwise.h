@@ -10,7 +10,7 @@ namespace cl {
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
 // transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
 // qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel; grad_norm: the partial
-// launch's grid, aux = buffers; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar.
+// launch's grid, aux = buffers; plosses: form 0 = cl_p_losses_mse, 4 | kind << 1 | (table given) = cl_p_losses_w; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
@@ -52,6 +52,11 @@ int mse_loss(const float* eps, const float* target, float* d_eps, float* loss, l
 int plosses_mse(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
                 float* per_sample, float* scratch, int B, long per, float gscale, float w_simple, float w_elbo,
                 hipStream_t st);
+// the same reduction with a per-timestep weight table (wt, optional) and rho = l2 (kind 0) or Huber (kind 1, delta);
+// EwLaunchRec: id = EW_PLOSSES, form = 4 | kind << 1 | (wt given)  (elementwise.hip)
+int plosses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, const float* wt, float* out,
+              float* per_sample, float* scratch, int B, long per, int kind, float delta, float gscale, float w_simple,
+              float w_elbo, hipStream_t st);
 int zero_bytes(void* p, long nbytes, hipStream_t st);
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
                     int C, int tap, int stride, int pad, hipStream_t st);

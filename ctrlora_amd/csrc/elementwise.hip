@@ -404,6 +404,61 @@ __global__ __launch_bounds__(64) void plosses_finish_kernel(const float* __restr
   out[0] = ls; out[1] = lv; out[2] = w_simple * ls + w_elbo * lv;
 }
 
+// The same reduction with a per-timestep weight and a choice of rho (cl_p_losses_w), in the geometry and summation order of the
+// two kernels above.  The launcher sends what those two already compute to them: l2 without a table to the partial kernel above,
+// any call without a table to the finishing kernel above (the per-sample means are unweighted either way).
+//   KIND 0 (l2)     rho(d) = d^2,                                                   rho'(d) = 2 d   (the 2 is in gmul)
+//   KIND 1 (Huber)  rho(d) = |d| <= delta ? d^2 / 2 : delta (|d| - delta / 2),      rho'(d) = clamp(d, -delta, delta)
+//   l_b = mean rho(d) of sample b (unweighted: scratch, per_sample, out[0], out[1]);  d_eps = rho'(d) * gmul * wt[t_b]
+//   out[2] = w_simple * mean_b (wt[t_b] l_b) + w_elbo * out[1]
+// t and wt are read on the device, once per workgroup: a captured launch follows both.
+template <int KIND>
+__global__ __launch_bounds__(256) void plosses_w_partial_kernel(const float* __restrict__ eps,
+                                                                const float* __restrict__ target,
+                                                                float* __restrict__ d_eps, float* __restrict__ scratch,
+                                                                const long* __restrict__ t, const float* __restrict__ wt,
+                                                                long per, float gmul, float delta) {
+  __shared__ float red[4];
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const long base = (long)b * per;
+  const long c0 = per * chunk / PL_CHUNKS, c1 = per * (chunk + 1) / PL_CHUNKS;
+  const float g = wt ? gmul * wt[t[b]] : gmul;
+  float acc = 0.f;
+  for (long i = c0 + threadIdx.x; i < c1; i += 256) {
+    const float d = eps[base + i] - target[base + i];
+    if (KIND == 0) {
+      acc += d * d;
+      if (d_eps) d_eps[base + i] = d * g;
+    } else {
+      const float a = fabsf(d);
+      acc += a <= delta ? 0.5f * d * d : delta * (a - 0.5f * delta);
+      if (d_eps) d_eps[base + i] = fminf(fmaxf(d, -delta), delta) * g;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) scratch[b * PL_CHUNKS + chunk] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(64) void plosses_w_finish_kernel(const float* __restrict__ scratch, const long* __restrict__ t,
+                                                              const float* __restrict__ lvlb, const float* __restrict__ wt,
+                                                              float* __restrict__ out, float* __restrict__ per_sample, int B,
+                                                              long per, float w_simple, float w_elbo) {
+  if (threadIdx.x != 0) return;
+  float ls = 0.f, lv = 0.f, lw = 0.f;
+  for (int b = 0; b < B; ++b) {
+    float s = 0.f;
+    for (int c = 0; c < PL_CHUNKS; ++c) s += scratch[b * PL_CHUNKS + c];
+    s /= (float)per;
+    if (per_sample) per_sample[b] = s;
+    ls += s;
+    if (lvlb) lv += lvlb[t[b]] * s;
+    lw += wt[t[b]] * s;
+  }
+  ls /= (float)B; lv /= (float)B; lw /= (float)B;
+  out[0] = ls; out[1] = lv; out[2] = w_simple * lw + w_elbo * lv;
+}
+
 // ---------------------------------------------------------------- DDIM update (ddim_hacked.py:192,203-231)
 // coef = device table [S][4] = {a_t, a_prev, sigma_t, sqrt(1 - a_t)} (fp32), row `index` is used.  x_prev may alias x
 // (element-wise), so neither is __restrict__.  One body for the host-index and the device-cursor launch (below): an eager
@@ -1182,6 +1237,24 @@ int plosses_mse(const float* eps, const float* target, float* d_eps, const long*
   hipLaunchKernelGGL(plosses_partial_kernel, grid, dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
   hipLaunchKernelGGL(plosses_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, out, per_sample, B, per, w_simple, w_elbo);
   return ew_done(EW_PLOSSES, -1, grid, 256);
+}
+int plosses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, const float* wt, float* out,
+              float* per_sample, float* scratch, int B, long per, int kind, float delta, float gscale, float w_simple,
+              float w_elbo, hipStream_t st) {
+  ew_rec_begin();
+  if (B < 1 || B > 65535 || per < 1) return CL_EINVAL;
+  if (!eps || !target || !out || !scratch || ((lvlb || wt) && !t)) return CL_EINVAL;
+  if (kind != 0 && kind != 1) return CL_EINVAL;
+  if (kind == 1 && !(std::isfinite(delta) && delta > 0.f)) return CL_EINVAL;
+  // rho' carries the 2 of l2 here; the table's factor is applied on the device (elementwise.hip: plosses_w_partial_kernel)
+  const float gmul = (kind == 0 ? 2.0f : 1.0f) * gscale * w_simple / ((float)per * (float)B);
+  const dim3 grid(PL_CHUNKS, B);
+  if (kind == 1) hipLaunchKernelGGL((plosses_w_partial_kernel<1>), grid, dim3(256), 0, st, eps, target, d_eps, scratch, t, wt, per, gmul, delta);
+  else if (wt) hipLaunchKernelGGL((plosses_w_partial_kernel<0>), grid, dim3(256), 0, st, eps, target, d_eps, scratch, t, wt, per, gmul, 0.f);
+  else hipLaunchKernelGGL(plosses_partial_kernel, grid, dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
+  if (wt) hipLaunchKernelGGL(plosses_w_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, wt, out, per_sample, B, per, w_simple, w_elbo);
+  else hipLaunchKernelGGL(plosses_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, out, per_sample, B, per, w_simple, w_elbo);
+  return ew_done(EW_PLOSSES, -1, grid, 256, 4 | (kind << 1) | (wt ? 1 : 0));
 }
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
                     int C, int tap, int stride, int pad, hipStream_t st) {

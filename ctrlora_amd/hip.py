@@ -109,6 +109,7 @@ _SIGS = {
     "cl_qsample": [_P, _P, _P, _P, _P, _P, _I, _L, _P],
     "cl_mse_loss": [_P, _P, _P, _P, _L, _F, _P],
     "cl_p_losses_mse": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
+    "cl_p_losses_w": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P, _I, _F, _P],
     "cl_zero": [_P, _L, _P],
     "cl_softmax_rows": [_I, _P, _L, _P, _L, _L, _I, _F, _P],
     "cl_conv_tap_gather": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -772,6 +773,22 @@ def p_losses_mse(eps, target, d_eps, t, lvlb, out3, scratch, gscale=1.0, w_simpl
     _chk(lib().cl_p_losses_mse(eps.data_ptr(), target.data_ptr(), ptr(d_eps), ptr(t), ptr(lvlb), out3.data_ptr(),
                                ptr(per_sample), scratch.data_ptr(), B, eps.numel() // B, gscale, w_simple, w_elbo,
                                stream()), "cl_p_losses_mse")
+    return out3
+
+
+LOSS_KINDS = {"l2": 0, "huber": 1}
+
+
+def p_losses_w(eps, target, d_eps, t, lvlb, out3, scratch, gscale=1.0, w_simple=1.0, w_elbo=0.0, per_sample=None, wt=None,
+               kind=0, delta=1.0):
+    """p_losses_mse with a per-timestep weight table `wt` (fp32 [T], indexed by t; None = all ones) and kind 0 = l2 / 1 = Huber
+    with `delta`: out3[0] and out3[1] stay unweighted, out3[2] and d_eps carry wt[t_b] (include/ctrlora_hip.h: cl_p_losses_w)."""
+    B = eps.shape[0]
+    assert scratch.numel() >= 16 * B and eps.is_contiguous() and target.is_contiguous()
+    assert wt is None or (wt.dtype == torch.float32 and wt.is_contiguous() and wt.device == eps.device)
+    _chk(lib().cl_p_losses_w(eps.data_ptr(), target.data_ptr(), ptr(d_eps), ptr(t), ptr(lvlb), out3.data_ptr(), ptr(per_sample),
+                             scratch.data_ptr(), B, eps.numel() // B, gscale, w_simple, w_elbo, ptr(wt), int(kind), float(delta),
+                             stream()), "cl_p_losses_w")
     return out3
 
 

@@ -71,23 +71,28 @@ class PLossFn(torch.autograd.Function):
     """LatentDiffusion.p_losses' reduction (ddpm.py:902-918 with logvar = 0) as ONE deterministic HIP reduction:
     returns the 3-vector {loss_simple, loss_vlb, loss = w_simple * loss_simple + w_elbo * loss_vlb} and keeps
     d(w_simple * loss_simple) / d eps for the backward (the elbo term is not differentiated; its weight is 0 in
-    every CtrLoRA config and the caller checks that)."""
+    every CtrLoRA config and the caller checks that).  `wt` (a per-timestep weight table, e.g. Min-SNR-gamma) and `kind` 1
+    (Huber with `delta`) go through cl_p_losses_w; without either the call is cl_p_losses_mse, as before."""
 
     @staticmethod
-    def forward(ctx, eps, target, t, lvlb, w_simple, w_elbo):
+    def forward(ctx, eps, target, t, lvlb, w_simple, w_elbo, wt=None, kind=0, delta=1.0):
         eps = eps.float().contiguous()
         target = target.float().contiguous()
         out = torch.empty(3, dtype=torch.float32, device=eps.device)
         scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
         d_eps = torch.empty_like(eps)
-        hip.p_losses_mse(eps, target, d_eps, t.long().contiguous(), lvlb, out, scratch, 1.0, float(w_simple), float(w_elbo))
+        if wt is None and kind == 0:
+            hip.p_losses_mse(eps, target, d_eps, t.long().contiguous(), lvlb, out, scratch, 1.0, float(w_simple), float(w_elbo))
+        else:
+            hip.p_losses_w(eps, target, d_eps, t.long().contiguous(), lvlb, out, scratch, 1.0, float(w_simple), float(w_elbo),
+                           wt=wt, kind=kind, delta=delta)
         ctx.save_for_backward(d_eps)
         return out
 
     @staticmethod
     def backward(ctx, g):
         (d_eps,) = ctx.saved_tensors
-        return d_eps * g[2], None, None, None, None, None
+        return d_eps * g[2], None, None, None, None, None, None, None, None
 
 
 class _AdamState:

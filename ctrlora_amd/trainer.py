@@ -49,7 +49,7 @@ def graph_step_refusal(model) -> Optional[str]:
                 "single-process): it keeps the eager loop")
     if not callable(getattr(model, "engine_train_step", None)):
         return f"{type(model).__name__} has no engine_train_step (the step without torch.autograd that a capture needs)"
-    if getattr(model, "loss_type", "l2") != "l2":
+    if getattr(model, "loss_type", "l2") not in ("l2", "huber"):       # "huber": cl_p_losses_w, not in the reference
         return f"engine_train_step computes the l2 loss only, the model's loss_type is '{model.loss_type}'"
     if float(getattr(model, "original_elbo_weight", 0.0)) != 0.0:
         return f"engine_train_step leaves the elbo term out, the model's original_elbo_weight is {model.original_elbo_weight}"

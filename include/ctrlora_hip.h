@@ -457,6 +457,23 @@ int cl_mse_loss(const float* eps, const float* target, float* d_eps, float* loss
 int cl_p_losses_mse(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
                     float* per_sample, float* scratch, int B, long per_sample_elems, float gscale, float w_simple,
                     float w_elbo, void* stream);
+/* The same reduction with a per-timestep weight and a choice of loss, added in ABI 7 (compatible).  Not in the reference: wt is
+ * meant for Min-SNR-gamma weights min(SNR_t, gamma) / SNR_t, kind 1 is torch.nn.functional.huber_loss.  With d = eps - target:
+ *   kind 0 (l2)     rho(d) = d^2,                                              rho'(d) = 2 d
+ *   kind 1 (Huber)  rho(d) = |d| <= delta ? d^2 / 2 : delta (|d| - delta / 2), rho'(d) = clamp(d, -delta, delta)
+ *   l_b = mean_chw rho(d)        per_sample[b] (optional) = l_b        (both unweighted)
+ *   out[0] = loss_simple = mean_b l_b (unweighted)      out[1] = loss_vlb = mean_b lvlb[t_b] l_b
+ *   out[2] = loss = w_simple * mean_b (wt[t_b] l_b) + w_elbo * loss_vlb
+ *   d_eps (optional) = gscale * w_simple * wt[t_b] * rho'(d) / (per_sample_elems * B)   (the elbo term is not differentiated)
+ * wt = fp32 [T] indexed by t_b, NULL = all ones; lvlb may be NULL; delta is read for kind 1 only.  t_b is not range-checked: the
+ * caller's tables hold an entry for every t it passes.  Deterministic (no float atomics, fixed summation order), no host
+ * synchronisation, no allocation; t, wt and lvlb are read from device memory, so a captured launch follows values that change
+ * between replays.  scratch: 16 * B floats.  With wt == NULL and kind == 0 every output has the bits of cl_p_losses_mse.
+ * Refused before anything is launched: what cl_p_losses_mse refuses (a null eps / target / out / scratch, B outside 1 .. 65535,
+ * per_sample_elems < 1, lvlb without t), wt without t, kind outside {0, 1}, kind 1 with a delta that is not finite or <= 0. */
+int cl_p_losses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
+                  float* per_sample, float* scratch, int B, long per_sample_elems, float gscale, float w_simple,
+                  float w_elbo, const float* wt, int kind, float delta, void* stream);
 /* optimizer.zero_grad() / accumulator clears without an ATen launch: a fill KERNEL on `stream` (not hipMemsetAsync: memset
    nodes of small buffers were mis-ordered when a step is replayed as several consecutive hipGraphs) */
 int cl_zero(void* p, long nbytes, void* stream);

@@ -38,6 +38,14 @@ class _LightningFree(nn.Module):
         self.last_logged = {k_: (float(v) if torch.is_tensor(v) and v.numel() == 1 else v) for k_, v in d.items()}
 
 
+def min_snr_weights(alphas_cumprod, gamma):
+    """Min-SNR-gamma loss weights for the eps-parameterisation, w_t = min(SNR_t, gamma) / SNR_t with SNR_t = acp_t / (1 - acp_t),
+    formed in float64 from the float64 schedule and rounded once to fp32 (Hang et al. 2023; not in the reference)."""
+    acp = np.asarray(alphas_cumprod, dtype=np.float64)
+    snr = acp / (1.0 - acp)
+    return torch.tensor(np.minimum(snr, float(gamma)) / snr, dtype=torch.float32)
+
+
 class DiffusionWrapper(nn.Module):
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
@@ -57,7 +65,7 @@ class DDPM(_LightningFree):
                  cosine_s=8e-3, given_betas=None, original_elbo_weight=0., v_posterior=0., l_simple_weight=1.,
                  conditioning_key=None, parameterization="eps", scheduler_config=None, use_positional_encodings=False,
                  learn_logvar=False, logvar_init=0., make_it_fit=False, ucg_training=None, reset_ema=False,
-                 reset_num_ema_updates=False, ema_decay=0.9999):
+                 reset_num_ema_updates=False, ema_decay=0.9999, min_snr_gamma=0.0, huber_delta=1.0):
         super().__init__()
         if parameterization != "eps" or learn_logvar:
             raise NotImplementedError("CtrLoRA configs: eps-parameterisation, fixed logvar")
@@ -66,6 +74,13 @@ class DDPM(_LightningFree):
                                       f"(ControlFinetuneLDM), not for {type(self).__name__}")
         if not 0.0 <= float(ema_decay) <= 1.0:
             raise ValueError(f"ema_decay={ema_decay!r} must lie in [0, 1]")
+        # Neither is in the reference.  min_snr_gamma > 0: the per-timestep loss weight min(SNR_t, gamma) / SNR_t (the buffer
+        # `loss_weights`, register_schedule); loss_type "huber": torch's huber_loss with huber_delta.
+        if not (np.isfinite(float(min_snr_gamma)) and float(min_snr_gamma) >= 0.0):
+            raise ValueError(f"min_snr_gamma={min_snr_gamma!r} must be finite and >= 0 (0 = off)")
+        if not (np.isfinite(float(huber_delta)) and float(huber_delta) > 0.0):
+            raise ValueError(f"huber_delta={huber_delta!r} must be finite and > 0")
+        self.min_snr_gamma, self.huber_delta = float(min_snr_gamma), float(huber_delta)
         self.parameterization, self.clip_denoised, self.log_every_t = parameterization, clip_denoised, log_every_t
         self.first_stage_key, self.image_size, self.channels = first_stage_key, image_size, channels
         self.model = DiffusionWrapper(unet_config, conditioning_key)
@@ -107,6 +122,37 @@ class DDPM(_LightningFree):
         lvlb = self.betas ** 2 / (2 * self.posterior_variance * f32(alphas) * (1 - self.alphas_cumprod))
         lvlb[0] = lvlb[1]
         self.register_buffer("lvlb_weights", lvlb, persistent=False)
+        # `loss_weights`: None (weighting off) or a non-persistent fp32 [num_timesteps] table the loss kernel indexes by t
+        self.register_buffer("loss_weights", None, persistent=False)
+        self.loss_weights_pinned = False     # set once a captured step holds the table's address -- or its absence
+        if self.min_snr_gamma > 0.0:
+            self.set_loss_weights(min_snr_weights(alphas_cumprod, self.min_snr_gamma))
+
+    @torch.no_grad()
+    def set_loss_weights(self, w):
+        """Per-timestep weights of the training loss: any finite, non-negative [num_timesteps] table, or None for none.  They
+        scale each sample's term of `loss` and of its gradient; the logged loss_simple / loss_vlb stay unweighted.  Once the
+        buffer exists a new table is copied INTO it, so a step captured earlier reads the new values; going from no table to a
+        table (or back) changes which kernel a captured step launches and is refused after a capture."""
+        have = self.loss_weights is not None
+        if (w is not None) != have and self.loss_weights_pinned:
+            raise RuntimeError("set_loss_weights: a captured training step " + ("reads the loss_weights buffer" if have else
+                               "was recorded without a loss_weights table") + "; switching weighting " +
+                               ("off" if have else "on") + " needs a new capture (set the table before the first step, or "
+                               "pass a table of ones instead of None)")
+        if w is None:
+            self.loss_weights = None
+            return
+        w = torch.as_tensor(w)
+        if tuple(w.shape) != (self.num_timesteps,):
+            raise ValueError(f"set_loss_weights: expected shape ({self.num_timesteps},), got {tuple(w.shape)}")
+        w32 = w.detach().to(dtype=torch.float32)
+        if not bool(torch.isfinite(w32).all()) or bool((w32 < 0).any()):
+            raise ValueError("set_loss_weights: the weights must be finite and non-negative")
+        if have:
+            self.loss_weights.copy_(w32)
+        else:
+            self.loss_weights = w32.to(self.betas.device).clone()
 
     def q_sample(self, x_start, t, noise=None):
         noise = default(noise, lambda: torch.randn_like(x_start))
@@ -123,6 +169,8 @@ class DDPM(_LightningFree):
             loss = (target - pred).abs()
         elif self.loss_type == "l2":
             loss = torch.nn.functional.mse_loss(target, pred, reduction="none")
+        elif self.loss_type == "huber":
+            loss = torch.nn.functional.huber_loss(pred, target, reduction="none", delta=self.huber_delta)
         else:
             raise NotImplementedError(f"unknown loss type '{self.loss_type}'")
         return loss.mean() if mean else loss
@@ -229,17 +277,22 @@ class LatentDiffusion(DDPM):
         model_output = self.apply_model(x_noisy, t, cond)
         prefix = "train" if self.training else "val"
         target = noise
-        if model_output.is_cuda and self.loss_type == "l2" and self.original_elbo_weight == 0.:
-            # logvar == 0 and original_elbo_weight == 0  =>  loss = l_simple_weight * mean((eps-target)^2); the three
-            # logged scalars come out of one deterministic HIP reduction
+        if model_output.is_cuda and self.loss_type in ("l2", "huber") and self.original_elbo_weight == 0.:
+            # logvar == 0 and original_elbo_weight == 0  =>  loss = l_simple_weight * mean_b (w[t_b] * mean rho(eps-target));
+            # the three logged scalars come out of one deterministic HIP reduction
             from ctrlora_amd.train import PLossFn
-            out = PLossFn.apply(model_output, target, t, self.lvlb_weights, self.l_simple_weight, 0.0)
+            # (no table and l2: PLossFn launches cl_p_losses_mse, as before; otherwise cl_p_losses_w)
+            out = PLossFn.apply(model_output, target, t, self.lvlb_weights, self.l_simple_weight, 0.0, self.loss_weights,
+                                int(self.loss_type == "huber"), self.huber_delta)
             loss = out[2]
             return loss, {f"{prefix}/loss_simple": out[0].detach(), f"{prefix}/loss_vlb": out[1].detach(),
                           f"{prefix}/loss": loss.detach()}
         loss_simple = self.get_loss(model_output, target, mean=False).mean([1, 2, 3])
         logvar_t = self.logvar[t].to(self.device)
-        loss = self.l_simple_weight * (loss_simple / torch.exp(logvar_t) + logvar_t).mean()
+        weighted = loss_simple / torch.exp(logvar_t) + logvar_t
+        if self.loss_weights is not None:
+            weighted = self.loss_weights[t] * weighted
+        loss = self.l_simple_weight * weighted.mean()
         loss_vlb = (self.lvlb_weights[t] * loss_simple).mean()
         loss = loss + self.original_elbo_weight * loss_vlb
         return loss, {f"{prefix}/loss_simple": loss_simple.mean(), f"{prefix}/loss_vlb": loss_vlb,

@@ -62,7 +62,32 @@ def get_parser():
                    help="keep an exponential moving average of the trained weights with this decay (LitEma's rule, warm-up "
                         "included; 0.9999 is its default), updated on the device inside every optimizer step and saved in the "
                         "checkpoints as model_ema.*; extract it with tool_extract_weights.py --ema; 0 = off (the default)")
+    add_loss_args(p)
     return p
+
+
+def add_loss_args(p):
+    """The flags of the training objective (the same three as in train_ctrlora_pretrain.py); none of them is in the reference."""
+    p.add_argument("--min_snr_gamma", type=float, default=0.0,
+                   help="weight each sample's loss by min(SNR_t, gamma) / SNR_t (Min-SNR-gamma; 5 is the paper's value), on the "
+                        "device and inside the step; 0 = off (the default)")
+    p.add_argument("--loss", choices=("l2", "huber"), default=None,
+                   help="the per-element loss: l2, or torch's huber_loss with --huber_delta (default: the config's loss_type)")
+    p.add_argument("--huber_delta", type=float, default=None,
+                   help="the Huber loss's threshold between its quadratic and its linear branch (default: the config's, 1.0)")
+
+
+def loss_model_params(min_snr_gamma: float = 0.0, loss=None, huber_delta=None) -> dict:
+    """--min_snr_gamma / --loss / --huber_delta: what create_model overrides in the config's model.params; nothing at the
+    defaults.  The model's constructor refuses a negative gamma and a non-positive delta."""
+    out = {}
+    if min_snr_gamma != 0.0:
+        out["min_snr_gamma"] = float(min_snr_gamma)
+    if loss is not None:
+        out["loss_type"] = loss
+    if huber_delta is not None:
+        out["huber_delta"] = float(huber_delta)
+    return out
 
 
 def _ema_decay(text):
@@ -144,7 +169,8 @@ def main(argv=None):
         print("Batch size per device:", args.bs)
         print("Gradient accumulation:", args.gradacc)
         print("Total batch size:", args.bs * world * args.gradacc)
-    model = create_model(args.config, params=ema_model_params(args.ema_decay)).cpu()
+    model = create_model(args.config, params={**ema_model_params(args.ema_decay),
+                                              **loss_model_params(args.min_snr_gamma, args.loss, args.huber_delta)}).cpu()
     model.learning_rate = args.lr
     model.sd_locked = True
     model.only_mid_control = False
