@@ -40,6 +40,44 @@ def _reference_module_rank(name: str) -> int:
     return _REFERENCE_TOP_LEVEL.index(head) if head in _REFERENCE_TOP_LEVEL else len(_REFERENCE_TOP_LEVEL)
 
 
+MAX_OPTIM_GROUPS = 8      # the rows of the optimizer's device table (ctrlora_amd.hip.ADAMW_MAX_GROUPS)
+
+
+def assign_optim_groups(names, rules):
+    """Split the trained tensors into optimizer parameter groups (not in the reference: its fine-tuning has one group).
+    `rules`: a list of {name, match: [substrings], lr_scale: 1.0, weight_decay: None}, applied to `names` in order -- a name
+    joins the FIRST rule one of whose substrings it contains; the names no rule takes form group 0, "default".  Returns
+    [{name, lr_scale, weight_decay, names}], "default" first, then the rules in their order.  A rule that matches nothing is a
+    mistake in the rule, not an empty group: ValueError."""
+    groups = [dict(name="default", lr_scale=1.0, weight_decay=None, names=[])]
+    for r in rules:
+        r = dict(r)
+        unknown = set(r) - {"name", "match", "lr_scale", "weight_decay"}
+        if unknown or "name" not in r or not r.get("match"):
+            raise ValueError(f"optim_groups rule {r}: keys are name, match (a non-empty list of substrings), lr_scale, weight_decay")
+        match = [r["match"]] if isinstance(r["match"], str) else [str(m) for m in r["match"]]
+        lr_scale = float(r.get("lr_scale", 1.0))
+        wd = r.get("weight_decay")
+        if not lr_scale > 0.0 or (wd is not None and not float(wd) >= 0.0):
+            raise ValueError(f"optim_groups rule '{r['name']}': lr_scale must be > 0 and weight_decay None or >= 0")
+        groups.append(dict(name=str(r["name"]), match=match, lr_scale=lr_scale, weight_decay=None if wd is None else float(wd),
+                           names=[]))
+    if len({g["name"] for g in groups}) != len(groups):
+        raise ValueError(f"optim_groups: the group names {[g['name'] for g in groups]} must differ ('default' is group 0)")
+    if len(groups) > MAX_OPTIM_GROUPS:
+        raise ValueError(f"optim_groups: {len(groups)} groups with 'default', at most {MAX_OPTIM_GROUPS}")
+    for n in names:
+        hit = next((g for g in groups[1:] if any(m in n for m in g["match"])), groups[0])
+        hit["names"].append(n)
+    for g in groups[1:]:
+        if not g["names"]:
+            raise ValueError(f"optim_groups rule '{g['name']}' (match {g['match']}) takes none of the {len(names)} trained "
+                             "tensors: an earlier rule took them all, or nothing carries such a name")
+    for g in groups:
+        g.pop("match", None)
+    return groups
+
+
 class ControlNetFinetune(ControlNet):
     def __init__(self, ft_with_lora=True, lora_rank=128, norm_trainable=True, zero_trainable=True, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -66,6 +104,8 @@ class ControlFinetuneLDM(ControlLDM):
     reset_ema).  The update runs once per OPTIMIZER step, inside the optimizer's own step (the reference's on_train_batch_end
     runs after every micro-batch)."""
     supports_ema = True
+    # `optim_groups` (a list of assign_optim_groups rules; None = one group, the state dict of before) and `scheduler_config`
+    # (a target with `.schedule(n)`, e.g. ctrlora_amd.lr_schedule.WarmupDecay) are honoured by configure_optimizers().
 
     # ---- EMA of the trained weights
     def _ema_named_params(self):
@@ -208,9 +248,27 @@ class ControlFinetuneLDM(ControlLDM):
         params = [bound[n] for n in names]
         print(f"Optimizable params: {sum(p.numel() for p in params) / 1e6:.1f}M")
         world = 1 if self.dp is None else self.dp.world_size
+        if self.optim_groups is not None:
+            # torch's list-of-dicts form: "default" takes the constructor's lr and weight decay, a rule scales / replaces them
+            params = []
+            for g in assign_optim_groups(names, list(self.optim_groups)):
+                d = dict(params=[bound[n] for n in g["names"]], name=g["name"], lr=self.learning_rate * g["lr_scale"])
+                if g["weight_decay"] is not None:
+                    d["weight_decay"] = g["weight_decay"]
+                params.append(d)
+                print(f"Parameter group '{g['name']}': {len(g['names'])} tensors, lr x {g['lr_scale']:g}"
+                      + ("" if g["weight_decay"] is None else f", weight decay {g['weight_decay']:g}"))
         opt = FusedAdamW(params, [ex], lr=self.learning_rate, grad_scale=1.0 / world)
         if self.dp is not None:
             opt.pre_step_hook = self.dp.wait
         if self.use_ema:
             opt.attach_ema(self.model_ema, [self._bind_ema()[1]])
-        return opt
+        if self.scheduler_config is None:
+            return opt
+        # the reference's shape (LatentDiffusion.configure_optimizers, ddpm.py:1288-1299): a LambdaLR stepped once per optimizer
+        # step; the Trainer compiles it to a device table for an engine optimizer (ctrlora_amd.lr_schedule.compile_lambda_lr)
+        from torch.optim.lr_scheduler import LambdaLR
+        from ldm.util import instantiate_from_config
+        sched = instantiate_from_config(self.scheduler_config)
+        print("Setting up LambdaLR scheduler...")
+        return [opt], [{"scheduler": LambdaLR(opt, lr_lambda=sched.schedule), "interval": "step", "frequency": 1}]

@@ -168,6 +168,7 @@ class _PretrainDP:
 
 
 class ControlPretrainLDM(ControlLDM):
+    refuses_lr_options = True      # scheduler_config / optim_groups: fine-tuning only (PretrainAdamW: one group, no device schedule)
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):

@@ -361,6 +361,8 @@ int cl_adamw_dev(float* p, const float* g, float* m, float* v, long n, const flo
 long cl_grad_norm_scratch_floats(int nbuf) { return grad_norm_scratch_floats(nbuf); }
 int cl_grad_norm(const float* const* bufs, const long* counts, int nbuf, const float* hyper, const float* max_norm, float* out, float* scratch, void* stream) { return grad_norm(bufs, counts, nbuf, hyper, max_norm, out, scratch, S(stream)); }
 int cl_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip, void* stream) { return adamw_dev_clip(p, g, m, v, n, hyper, step, clip, S(stream)); }
+int cl_adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const float* hyper_table, int ngroups, const unsigned char* chunk_group, int* step, const float* clip, void* stream) { return adamw_dev_groups(p, g, m, v, n, hyper_table, ngroups, chunk_group, step, clip, S(stream)); }
+int cl_lr_schedule(float* hyper_table, int ngroups, const float* lr_table, int T, const int* step, void* stream) { return lr_schedule(hyper_table, ngroups, lr_table, T, step, S(stream)); }
 int cl_ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, void* stream) { return ema_update(shadow, p, n, decay, num_updates, S(stream)); }
 int cl_swap(float* a, float* b, long n, void* stream) { return swap_buffers(a, b, n, S(stream)); }
 int cl_ddim_set_t(const long* table, const int* cursor, int S_, long* ts, int n, void* stream) { return ddim_set_t(table, cursor, S_, ts, n, S(stream)); }

@@ -19,6 +19,8 @@ enum {
   EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV,
   EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP
 };
+// appended after EW_SWAP (41): adamw_dev_groups: form 1 = with a clip coefficient, aux = groups; lr_schedule: aux = groups
+enum { EW_ADAMW_DEV_GROUPS = EW_SWAP + 1, EW_LR_SCHEDULE };
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
   int dtype;     // CL_BF16 / CL_F32 of the typed launchers (transpose: the output's), -1 where there is no dtype argument
@@ -72,6 +74,11 @@ int grad_norm(const float* const* bufs, const long* counts, int nbuf, const floa
               float* scratch, hipStream_t st);
 int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
                    hipStream_t st);
+// AdamW over one flat buffer whose 64-float chunks belong to 1 .. 8 parameter groups (hyper_table [ngroups][6], chunk_group
+// [n / 64]; clip may be NULL); the groups' learning rates of this step from a device [T][ngroups] table (elementwise.hip)
+int adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const float* hyper_table, int ngroups,
+                     const unsigned char* chunk_group, int* step, const float* clip, hipStream_t st);
+int lr_schedule(float* hyper_table, int ngroups, const float* lr_table, int T, const int* step, hipStream_t st);
 // LitEma.forward over one flat fp32 buffer with device-resident decay and update count; exchange of two flat fp32 buffers
 // (elementwise.hip)
 int ema_update(float* shadow, const float* p, long n, const float* decay, const int* num_updates, hipStream_t st);

@@ -609,6 +609,75 @@ __global__ void adamw_dev_clip_kernel(float* __restrict__ p, const float* __rest
   }
 }
 
+// ---------------------------------------------------------------- AdamW with parameter groups, learning rates from a device table
+// adamw_dev_kernel / adamw_dev_clip_kernel over one flat buffer whose 64-float chunks belong to up to AG_MAX_GROUPS groups:
+// table = [ngroups][6] rows of cl_adamw_dev's hyper, chunk_group[c] = the group of elements [64 c, 64 c + 64).  The flat buffers
+// align every tensor to 64 floats (packing.TrainableSet.materialize), so a chunk never holds two tensors.  A wave owns one chunk
+// per trip: its 64 lanes read and write one whole 256-byte line of each of the four streams, exactly the access of the
+// one-group kernels (lane = consecutive float), and the group is ONE byte load per wave and trip (all lanes read the same address,
+// made wave-uniform with readfirstlane) -- 1 / 64 byte per element next to the 28 the streams move.  The first `ngroups` threads of
+// a workgroup derive the group's scalars once (the bias corrections from the shared step counter, the same powf / sqrtf on the
+// same operands as the one-group kernels) and leave them in LDS.  An entry >= ngroups is clamped to the last group: nothing is
+// read beyond the table.
+// The bits are those of adamw_dev_kernel / adamw_dev_clip_kernel over the chunk with the group's row as `hyper`.  Those two are
+// compiled with hipcc's default contraction, which fuses two of their operations and no other; this kernel states that outcome
+// instead of leaving it to the optimizer (with the scalars in LDS it fuses a third): contraction is off here and the two fused
+// operations are written as fmaf --
+//     1 - lr wd           = fma(-lr, wd, 1)
+//     m' = b1 m + (1 - b1) gi = fma(1 - b1, gi, b1 m)
+//     v' = b2 v + ((1 - b2) gi) gi,  p' = (1 - lr wd) p - ((lr / bc1) m') / (sqrt(v') / bc2_sqrt + eps):  every operation rounded
+// tests/test_gpu_optim_groups.py holds the two families to each other bit for bit, so a compiler that contracts the one-group
+// kernels differently shows there.
+constexpr int AG_MAX_GROUPS = 8;
+struct AdamGroup { float decay, beta1, omb1, beta2, omb2, bc2_sqrt, eps, lr_bc1, gscale; };
+__device__ __forceinline__ AdamGroup adam_group(const float* __restrict__ hyper, float st, const float* __restrict__ clip) {
+#pragma clang fp contract(off)
+  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4];
+  const float gscale = clip ? hyper[5] * clip[1] : hyper[5];
+  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
+  return AdamGroup{__builtin_fmaf(-lr, wd, 1.0f), beta1, 1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, lr / bc1, gscale};
+}
+__device__ __forceinline__ void adam_elem(const AdamGroup& h, float& pi, float g, float& mi, float& vi) {
+#pragma clang fp contract(off)
+  const float gi = g * h.gscale;
+  const float pd = pi * h.decay;
+  mi = __builtin_fmaf(h.omb1, gi, h.beta1 * mi);
+  vi = h.beta2 * vi + h.omb2 * gi * gi;
+  const float denom = sqrtf(vi) / h.bc2_sqrt + h.eps;
+  pi = pd - h.lr_bc1 * mi / denom;
+}
+__global__ __launch_bounds__(256) void adamw_dev_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, long nchunks,
+                                                               const float* __restrict__ table, int ngroups,
+                                                               const unsigned char* __restrict__ chunk_group,
+                                                               const int* __restrict__ step, const float* __restrict__ clip) {
+  __shared__ AdamGroup hp[AG_MAX_GROUPS];
+  if ((int)threadIdx.x < ngroups) hp[threadIdx.x] = adam_group(table + 6 * threadIdx.x, (float)*step, clip);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+  for (long c = wave; c < nchunks; c += nwaves) {
+    int grp = __builtin_amdgcn_readfirstlane((int)chunk_group[c]);
+    grp = grp < ngroups ? grp : ngroups - 1;
+    const AdamGroup h = hp[grp];
+    const long i = (c << 6) + lane;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(h, pi, g[i], mi, vi);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+
+// table[gidx][0] = lr_table[min(*step - 1, T - 1)][gidx]: the learning rate of optimizer step *step (counted from 1, already
+// advanced by tick_kernel) from a device [T][ngroups] table -- LambdaLR's indexing, the last row holds past the end.
+__global__ void lr_schedule_kernel(float* __restrict__ table, int ngroups, const float* __restrict__ lr_table, int T,
+                                   const int* __restrict__ step) {
+  const int gidx = threadIdx.x;
+  if (gidx >= ngroups) return;
+  int row = *step - 1;
+  row = row < 0 ? 0 : (row < T - 1 ? row : T - 1);
+  table[6 * gidx] = lr_table[(long)row * ngroups + gidx];
+}
+
 // ---------------------------------------------------------------- EMA of the trained weights (ldm/modules/ema.py: LitEma.forward)
 // shadow -= (1 - d) * (shadow - p) over one flat fp32 buffer, d = min(*decay, (1 + u) / (10 + u)) with u = *num_updates already
 // advanced by tick_kernel, or *decay itself for u < 0 (LitEma without the warm-up).  Decay and count are read from device memory:
@@ -1345,6 +1414,22 @@ int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const f
   const dim3 grid(ew_grid(n));
   hipLaunchKernelGGL(adamw_dev_clip_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step, clip);
   return ew_done(EW_ADAMW_DEV_CLIP, -1, grid, 256);
+}
+int adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const float* hyper_table, int ngroups,
+                     const unsigned char* chunk_group, int* step, const float* clip, hipStream_t st) {
+  ew_rec_begin();
+  if (!p || !g || !m || !v || !hyper_table || !chunk_group || !step) return CL_EINVAL;      // clip may be NULL: no clipping
+  if (n <= 0 || n % 64 != 0 || ngroups < 1 || ngroups > AG_MAX_GROUPS) return CL_EINVAL;
+  const dim3 grid(ew_grid(n));                 // a wave per 64-float chunk and trip: n / 64 chunks over 4 waves a workgroup
+  hipLaunchKernelGGL(adamw_dev_groups_kernel, grid, dim3(256), 0, st, p, g, m, v, n / 64, hyper_table, ngroups, chunk_group, step,
+                     clip);
+  return ew_done(EW_ADAMW_DEV_GROUPS, -1, grid, 256, clip ? 1 : 0, ngroups);
+}
+int lr_schedule(float* hyper_table, int ngroups, const float* lr_table, int T, const int* step, hipStream_t st) {
+  ew_rec_begin();
+  if (!hyper_table || !lr_table || !step || T < 1 || ngroups < 1 || ngroups > AG_MAX_GROUPS) return CL_EINVAL;
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, st, hyper_table, ngroups, lr_table, T, step);
+  return ew_done(EW_LR_SCHEDULE, -1, dim3(1), 64, 0, ngroups);
 }
 // The two-buffer streaming launches: form 1 = 16-byte accesses (both buffers the same distance from a 16-byte boundary) with a
 // scalar head and tail, form 0 = one element per work item; aux = the 16-byte vectors.

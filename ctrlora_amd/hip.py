@@ -132,6 +132,8 @@ _SIGS = {
     "cl_adamw_dev_clip": [_P, _P, _P, _P, _L, _P, _P, _P, _P],
     "cl_ema_update": [_P, _P, _L, _P, _P, _P],
     "cl_swap": [_P, _P, _L, _P],
+    "cl_adamw_dev_groups": [_P, _P, _P, _P, _L, _P, _I, _P, _P, _P, _P],
+    "cl_lr_schedule": [_P, _I, _P, _I, _P, _P],
 }
 _LONG_RESULT = ("cl_groupnorm_ws_floats", "cl_grad_norm_scratch_floats")
 EXPORTED = tuple(_SIGS.keys())
@@ -860,6 +862,32 @@ def adamw_dev_clip(p, g, m, v, hyper, step, clip):
     """adamw_dev on g * (grad_scale * clip[1]); clip = grad_norm's out.  clip[1] == 1 gives adamw_dev's bits."""
     _chk(lib().cl_adamw_dev_clip(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(),
                                  step.data_ptr(), clip.data_ptr(), stream()), "cl_adamw_dev_clip")
+
+
+ADAMW_MAX_GROUPS = 8
+ADAMW_CHUNK = 64       # floats per entry of a chunk_group map: the alignment of every tensor in a flat buffer
+
+
+def adamw_dev_groups(p, g, m, v, hyper_table, chunk_group, step, clip=None):
+    """adamw_dev (adamw_dev_clip with `clip` = grad_norm's out) over one flat buffer whose 64-float chunks belong to the
+    parameter groups of `hyper_table` (fp32 [G, 6], G <= 8): `chunk_group` (uint8 [numel / 64]) names each chunk's group."""
+    assert hyper_table.dtype == torch.float32 and hyper_table.is_contiguous() and hyper_table.dim() == 2 and \
+        hyper_table.shape[1] == 6, (hyper_table.dtype, tuple(hyper_table.shape))
+    assert chunk_group.dtype == torch.uint8 and chunk_group.is_contiguous() and chunk_group.numel() * ADAMW_CHUNK == p.numel(), \
+        (chunk_group.dtype, chunk_group.numel(), p.numel())
+    _chk(lib().cl_adamw_dev_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper_table.data_ptr(),
+                                   hyper_table.shape[0], chunk_group.data_ptr(), step.data_ptr(), ptr(clip), stream()),
+         "cl_adamw_dev_groups")
+
+
+def lr_schedule(hyper_table, lr_table, step):
+    """hyper_table[k, 0] = lr_table[min(step - 1, T - 1), k] on the device: `lr_table` fp32 [T, G], `step` the counter after
+    tick().  One small launch, capturable: a replayed step follows the table."""
+    assert hyper_table.dtype == lr_table.dtype == torch.float32 and step.dtype == torch.int32
+    assert hyper_table.is_contiguous() and lr_table.is_contiguous() and lr_table.dim() == 2 and \
+        lr_table.shape[1] == hyper_table.shape[0] and hyper_table.shape[1] == 6, (tuple(hyper_table.shape), tuple(lr_table.shape))
+    _chk(lib().cl_lr_schedule(hyper_table.data_ptr(), hyper_table.shape[0], lr_table.data_ptr(), lr_table.shape[0],
+                              step.data_ptr(), stream()), "cl_lr_schedule")
 
 
 def ema_update(shadow, p, decay, num_updates):

@@ -7,7 +7,9 @@
                       (ddpm.py:902-918 with logvar = 0).
   * FusedAdamW     -- torch.optim.AdamW semantics (cldm_ctrlora_finetune.py:105) as ONE kernel over the
                       flat master/grad buffers, followed by the re-pack of the trainables; with `attach_ema()` the EMA of
-                      the trained weights (ldm/modules/ema.py) is one more kernel per bank inside the same step.
+                      the trained weights (ldm/modules/ema.py) is one more kernel per bank inside the same step.  torch's
+                      parameter groups (up to 8: cl_adamw_dev_groups, still one launch per bank) and a learning-rate curve kept
+                      in device memory (`set_lr_schedule`: cl_lr_schedule inside the step) are part of the same step.
   * PretrainAdamW  -- the same over the base buffer and every LoRA bank that has joined (both: _FlatAdamW + _AdamState).
   * bind_trainables -- re-points the ControlNet's trainable nn.Parameters at the flat buffers.
   * GraphedTrainStep -- the optimizer step as hipGraph replays of the pieces capture_plan() lists.
@@ -181,11 +183,48 @@ def _legacy_format_1(ts, src):
     return [(0, 0, src.numel())]
 
 
+def build_chunk_group(items, numel, group_of, ngroups):
+    """The uint8 map cl_adamw_dev_groups reads, on the host: entry c = the group of elements [64 c, 64 c + 64) of a flat buffer
+    of `numel` floats laid out by packing.TrainableSet.materialize (every tensor starts on a 64-float boundary and owns its
+    padding).  `items`: the Trainables, `group_of`: name -> group index.  Refuses what the kernel would have to clamp."""
+    from .engine.packing import rup
+    if not 1 <= ngroups <= hip.ADAMW_MAX_GROUPS:
+        raise ValueError(f"{ngroups} parameter groups: the grouped AdamW launch takes 1 to {hip.ADAMW_MAX_GROUPS}")
+    if numel % hip.ADAMW_CHUNK:
+        raise ValueError(f"a flat buffer of {numel} floats is not a whole number of {hip.ADAMW_CHUNK}-float chunks")
+    out = torch.zeros(numel // hip.ADAMW_CHUNK, dtype=torch.uint8)
+    for t in items:
+        if t.name not in group_of:
+            raise ValueError(f"trainable tensor '{t.name}' is in no parameter group")
+        k, n = int(group_of[t.name]), 1
+        for s in t.shape:
+            n *= s
+        if not 0 <= k < ngroups:
+            raise ValueError(f"'{t.name}' names group {k}, the table has {ngroups}")
+        if t.offset % hip.ADAMW_CHUNK or t.offset + rup(n, hip.ADAMW_CHUNK) > numel:
+            raise ValueError(f"'{t.name}' at offset {t.offset} ({n} floats) does not sit on whole chunks of the flat buffer")
+        out[t.offset // hip.ADAMW_CHUNK:(t.offset + rup(n, hip.ADAMW_CHUNK)) // hip.ADAMW_CHUNK] = k
+    return out
+
+
 class _FlatAdamW(torch.optim.Optimizer):
     """What the two optimizers over the engine's flat buffers share; a subclass launches its kernels in `_update()` and
     `zero_grad()`.  `params` are the bound nn.Parameters (kept in param_groups for scheduler / checkpoint compatibility); step
     counts and hyper-parameters live in DEVICE memory (cl_adamw_dev), so that `step()` can be captured in a hipGraph and
-    replayed: a schedule only has to refresh the 6-float `hyper` tensor (`sync_hyper()`, automatic outside capture).
+    replayed.
+
+    Parameter groups: `params` may be torch's list of group dicts (up to 8; an optional "name" each).  The hyper-parameters are a
+    [G, 6] device table, one row {lr, beta1, beta2, eps, weight_decay, grad_scale} per group; `_hyper` is row 0 (the whole table
+    of a one-group optimizer, as before).  `sync_hyper()` (automatic outside capture) pushes every row that changed on the host.
+    `grad_scale` is common to all groups.  What a subclass launches with more than one group is its own business (FusedAdamW:
+    cl_adamw_dev_groups); with one group nothing changes.
+
+    Learning-rate schedule: a host scheduler that moves `param_groups[k]["lr"]` reaches the device with the next `sync_hyper()`,
+    a host-to-device copy between replays.  `set_lr_schedule(table)` keeps the whole curve in device memory instead: an fp32
+    [T, G] table whose row `step - 1` cl_lr_schedule writes into the lr column right after the step's cl_tick, inside the captured
+    step.  While a table is set the device owns the lr column (`sync_hyper()` leaves it alone) and `param_groups[k]["lr"]` is a
+    mirror for logs and checkpoints; `last_lr()` is the column itself.  Setting or dropping a table changes what is launched: do
+    it before a capture, not after (refused); copying new values into a table of the same shape is allowed between replays.
 
     Global gradient norm (torch.nn.utils.clip_grad_norm_ with norm_type 2, on the device): `max_grad_norm` (None or <= 0: off)
     clips, `track_grad_norm` measures without clipping.  With either on, `_update()` opens with cl_grad_norm over the buffers the
@@ -195,9 +234,21 @@ class _FlatAdamW(torch.optim.Optimizer):
 
     def __init__(self, params, device, lr, betas, eps, weight_decay, grad_scale):
         super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        G = len(self.param_groups)
+        if G > hip.ADAMW_MAX_GROUPS:
+            raise ValueError(f"{G} parameter groups: the device table holds at most {hip.ADAMW_MAX_GROUPS}")
+        if G > 1:
+            for k, g in enumerate(self.param_groups):
+                g.setdefault("name", "default" if k == 0 else f"group{k}")
+            names = self.group_names
+            if len(set(names)) != G:
+                raise ValueError(f"parameter groups need distinct names, got {names}")
         self.grad_scale = grad_scale
-        self._hyper = torch.zeros(6, dtype=torch.float32, device=device)
-        self._hyper_host = None
+        self._hyper_table = torch.zeros(G, 6, dtype=torch.float32, device=device)
+        self._hyper = self._hyper_table[0]        # group 0's row: the table of a one-group optimizer, and grad_scale for cl_grad_norm
+        self._hyper_host = [None] * G
+        self._lr_table = None         # set_lr_schedule: fp32 [T, G] in device memory
+        self._captured = False        # a capture has recorded this optimizer's launches
         self.max_grad_norm, self.track_grad_norm = None, False
         self._max_norm = torch.zeros(1, dtype=torch.float32, device=device)      # the threshold; 0 = tracking only
         self._max_norm_host = 0.0
@@ -206,21 +257,72 @@ class _FlatAdamW(torch.optim.Optimizer):
         self.pre_step_hook = None     # e.g. DP: wait for the gradient all-reduce
         self.sync_hyper()
 
+    @property
+    def group_names(self):
+        return [g.get("name", "default") for g in self.param_groups]
+
     def sync_hyper(self):
-        """Push {lr, betas, eps, weight_decay, grad_scale} to the device if they changed (host -> device copy:
-        call it OUTSIDE graph capture / between replays)."""
-        g = self.param_groups[0]
-        cur = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-               float(self.grad_scale))
-        if cur != self._hyper_host:
-            self._hyper.copy_(torch.tensor(cur, dtype=torch.float32))
-            self._hyper_host = cur
+        """Push every group's {lr, betas, eps, weight_decay, grad_scale} to the device if they changed (host -> device copy:
+        call it OUTSIDE graph capture / between replays).  With a device schedule set the lr column is the device's."""
+        scheduled = self._lr_table is not None
+        for k, g in enumerate(self.param_groups):
+            cur = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                   float(self.grad_scale))
+            old = self._hyper_host[k]
+            if scheduled and old is not None:
+                if cur[1:] != old[1:]:
+                    self._hyper_table[k, 1:].copy_(torch.tensor(cur[1:], dtype=torch.float32))
+                self._hyper_host[k] = (old[0],) + cur[1:]         # old[0]: the last lr the HOST wrote
+            elif cur != old:
+                self._hyper_table[k].copy_(torch.tensor(cur, dtype=torch.float32))
+                self._hyper_host[k] = cur
         mx = float(self.max_grad_norm) if self.max_grad_norm is not None and self.max_grad_norm > 0 else 0.0
         if mx != self._max_norm_host:
             self._max_norm.copy_(torch.tensor([mx], dtype=torch.float32))
             self._max_norm_host = mx
         if self.norm_enabled and self._norm_scratch is None:      # allocated here: never inside a capture
             self._norm_scratch = torch.empty(hip.grad_norm_scratch_floats(), dtype=torch.float32, device=self._hyper.device)
+
+    def set_lr_schedule(self, table):
+        """Keep the learning-rate curve in device memory: `table` is fp32 [T, G] (row s - 1 = the groups' lr of optimizer step s,
+        the last row holds beyond T; `ctrlora_amd.lr_schedule.compile_lambda_lr` makes one from a LambdaLR), or [T], the same lr
+        for every group, or None = no device schedule (the host's `param_groups[k]["lr"]` goes back to the device).  A table of
+        the shape already set is copied into the same tensor, which a captured step keeps reading."""
+        G = len(self.param_groups)
+        if table is None:
+            if self._lr_table is None:
+                return
+            if self._captured:
+                raise RuntimeError("set_lr_schedule(None) after a capture: the captured step launches cl_lr_schedule; drop the "
+                                   "schedule before capturing")
+            self._lr_table = None
+            self._hyper_host = [None] * G
+            self.sync_hyper()
+            return
+        t = torch.as_tensor(table, dtype=torch.float32).detach()
+        if t.dim() == 1:
+            t = t[:, None].expand(t.shape[0], G)
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != G:
+            raise ValueError(f"a learning-rate table is [T] or [T, {G}] (one column per parameter group) with T >= 1, got "
+                             f"{tuple(t.shape)}")
+        if self._lr_table is not None and self._lr_table.shape == t.shape:
+            self._lr_table.copy_(t)
+            return
+        if self._captured:
+            raise RuntimeError("set_lr_schedule after a capture: " + ("the captured step holds the address and length of the table "
+                               "it was recorded with; only a table of the same shape can replace its values" if self._lr_table
+                               is not None else "the captured step does not launch cl_lr_schedule; set the schedule before capturing"))
+        self._lr_table = t.to(self._hyper_table.device).contiguous().clone()
+
+    def last_lr(self):
+        """The groups' learning rates as the device has them (a view of the table's lr column; no synchronization)."""
+        return self._hyper_table[:, 0]
+
+    def _tick_and_schedule(self, step):
+        """One tick of `step` and, with a device schedule, this step's learning rates, before any AdamW launch."""
+        hip.tick(step)
+        if self._lr_table is not None:
+            hip.lr_schedule(self._hyper_table, self._lr_table, step)
 
     @property
     def norm_enabled(self) -> bool:
@@ -248,14 +350,24 @@ class _FlatAdamW(torch.optim.Optimizer):
             self.pre_step_hook()
         if not torch.cuda.is_available() or not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
+        else:
+            self._captured = True         # from here on what `_update()` launches is fixed (set_lr_schedule)
         self._update()
         return loss
 
     def _saved_param_groups(self):
         return [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
 
+    def _check_group_structure(self, sd):
+        """Raise if `sd` was saved under other parameter groups; nothing is written."""
+        saved = [g.get("name", "default") for g in (sd.get("param_groups") or [{}])]
+        if saved != self.group_names:
+            raise ValueError(f"optimizer state was saved with the parameter groups {saved}, this optimizer has "
+                             f"{self.group_names}: resume with the group options of the run that wrote it")
+
     def _restore_param_groups(self, sd):
-        """Resume: the saved hyper-parameters (a scheduler may have moved lr) replace the constructor's, then go to the device."""
+        """Resume: the saved hyper-parameters (a scheduler may have moved lr) replace the constructor's, then go to the device
+        (under a device schedule the lr is a mirror only: the restored step counter puts the device back on the curve)."""
         for g, saved in zip(self.param_groups, sd.get("param_groups") or []):
             for k, v in saved.items():
                 if k != "params":
@@ -265,7 +377,10 @@ class _FlatAdamW(torch.optim.Optimizer):
 
 class FusedAdamW(_FlatAdamW):
     """AdamW over the engine's flat buffers for fine-tuning: one HIP kernel per ControlNet bank, all banks on ONE step
-    counter, each followed by the re-pack of its trainables."""
+    counter, each followed by the re-pack of its trainables.  With more than one parameter group (`params` a list of group
+    dicts, e.g. LoRA+'s higher lr for the up matrices, no weight decay on norms and biases) the kernel is cl_adamw_dev_groups:
+    still one launch per bank, every 64-float chunk of the flat buffer under its own group's row (`_chunk_group`, one uint8 map
+    per bank, built here from the bank's offsets and the groups the bound parameters were put in)."""
 
     def __init__(self, params, executors, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale: float = 1.0):
         self.executors = list(executors)
@@ -274,6 +389,24 @@ class FusedAdamW(_FlatAdamW):
         self._step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._states = [_AdamState(ex.tr, self._step_dev, partial(_legacy_rounds_1_3, ex)) for ex in self.executors]
         self.ema, self._ema_flats = None, None
+        self._chunk_group = self._build_chunk_groups() if len(self.param_groups) > 1 else None
+
+    def _build_chunk_groups(self):
+        """One chunk -> group map per bank, in device memory (allocated here: never inside a capture).  A bound parameter is a
+        view of its tensor's master storage (bind_trainables), so the storage address says which tensor a parameter is."""
+        group_at = {}
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                group_at[p.data_ptr()] = k        # torch has refused a parameter in two groups already
+        maps = []
+        for ex in self.executors:
+            missing = [t.name for t in ex.tr.items if t.master.data_ptr() not in group_at]
+            if missing:
+                raise ValueError(f"{len(missing)} trainable tensors are in no parameter group, e.g. {missing[:3]}")
+            group_of = {t.name: group_at[t.master.data_ptr()] for t in ex.tr.items}
+            cg = build_chunk_group(ex.tr.items, ex.tr.flat.numel(), group_of, len(self.param_groups))
+            maps.append(cg.to(ex.tr.flat.device))
+        return maps
 
     def attach_ema(self, ema, flats):
         """EMA of the trained weights inside the step (ldm.modules.ema.ModelEma bound to the executors; `flats`: its flat shadow
@@ -308,12 +441,15 @@ class FusedAdamW(_FlatAdamW):
 
     def _update(self):
         clip = self._grad_norm([ex.tr.flat_grad for ex in self.executors])
-        hip.tick(self._step_dev)          # one tick per optimizer step, however many banks follow
+        self._tick_and_schedule(self._step_dev)     # one tick per optimizer step, however many banks follow; then this step's lr
         ema = self.ema
         if ema is not None and ema.use_num_updates:
             hip.tick(ema.num_updates)     # LitEma counts before it averages; without the warm-up the count stays at -1
         for k, (ex, st) in enumerate(zip(self.executors, self._states)):
-            if clip:
+            if self._chunk_group is not None:
+                hip.adamw_dev_groups(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper_table, self._chunk_group[k],
+                                     self._step_dev, self.grad_norm_out if clip else None)
+            elif clip:
                 hip.adamw_dev_clip(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev, self.grad_norm_out)
             else:
                 hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
@@ -333,6 +469,7 @@ class FusedAdamW(_FlatAdamW):
 
     def load_state_dict(self, sd):
         assert len(sd["m"]) == len(self._states), "optimizer state was saved for a different number of ControlNet banks"
+        self._check_group_structure(sd)
         _load_states([(st, dict(m=m, v=v, step=sd["step"]), False) for st, m, v in zip(self._states, sd["m"], sd["v"])])
         self._restore_param_groups(sd)
 
@@ -352,10 +489,18 @@ class PretrainAdamW(_FlatAdamW):
     def __init__(self, params, executor, banks, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
         self.executor, self.executors, self.banks = executor, [executor], dict(banks)
         super().__init__(params, executor.tr.flat.device, lr, betas, eps, weight_decay, grad_scale)
+        if len(self.param_groups) > 1:
+            raise NotImplementedError("PretrainAdamW takes one parameter group: groups are built for fine-tuning only "
+                                      "(FusedAdamW), as the EMA is")
         mk = lambda ts: _AdamState(ts, legacy=partial(_legacy_format_1, ts))
         self._base = mk(executor.tr)
         self._bank_state = {k: mk(ts) for k, ts in self.banks.items()}
         self.active = []                 # tasks whose bank has received a gradient at least once, in order of first use
+
+    def set_lr_schedule(self, table):
+        if table is not None:
+            raise NotImplementedError("PretrainAdamW has no device learning-rate schedule: every bank counts its own steps; "
+                                      "built for fine-tuning only (FusedAdamW), as the EMA is")
 
     def mark_used(self, task):
         if task not in self.active:

@@ -19,6 +19,14 @@ micro-step), and / or tracking that norm as `train/grad_norm`.  The engine's opt
 step (`ctrlora_amd.train._FlatAdamW`), so it replays with the rest of a captured step; any other optimizer goes through
 `torch.nn.utils.clip_grad_norm_`.  Clipping by value is not offered.
 
+Learning-rate schedulers: `configure_optimizers()` may return a bare optimizer, `[opt]`, `([opt], [sched | {"scheduler": sched,
+"interval": "step"}])` or `{"optimizer": opt, "lr_scheduler": sched | {...}}` (Lightning's forms, one optimizer).  The scheduler
+is stepped once per OPTIMIZER step, after the last accumulation micro-step; `"interval": "epoch"` is refused.  For an engine
+optimizer a `LambdaLR` is compiled to a table of `max_steps` rows that the optimizer keeps in device memory and reads inside its
+own (captured) step (`_FlatAdamW.set_lr_schedule`); the host scheduler is still stepped, as the mirror that is logged (`train/lr`,
+or `train/lr/<group>` with parameter groups) and saved (`lr_schedulers` in the checkpoint).  Any other scheduler class moves the
+lr on the host (`scheduler.step()` + `sync_hyper()`), which `graph_step` refuses.
+
 `graph_step=True` (LoRA fine-tuning on a GPU only; off by default) replays the optimizer step as hipGraphs
 (`ctrlora_amd.train.GraphedTrainStep`) instead of launching its ~1900 kernels one by one: see `Trainer._fit_graphed`.
 """
@@ -88,6 +96,9 @@ class Trainer:
         self.current_epoch = 0
         self.model = None
         self.optimizer = None
+        self.lr_scheduler = None        # the one scheduler configure_optimizers() returned, or None
+        self._lr_on_device = False      # an engine optimizer reads the compiled curve from device memory
+        self.logged_lr = []             # (global_step, {"train/lr[/<group>]": lr the step used}) at log_every_n_steps
         self.logged = []
         # graph_step: False = the eager loop; True or a dict of options = captured steps (_fit_graphed)
         self.graph_step = bool(graph_step) or isinstance(graph_step, dict)
@@ -148,8 +159,11 @@ class Trainer:
             return
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         opt_state = self.optimizer.state_dict() if hasattr(self.optimizer, "state_dict") else None
-        torch.save({"state_dict": self.model.state_dict(), "global_step": self.global_step,
-                    "epoch": self.current_epoch, "optimizer_states": [opt_state]}, path)
+        ck = {"state_dict": self.model.state_dict(), "global_step": self.global_step,
+              "epoch": self.current_epoch, "optimizer_states": [opt_state]}
+        if self.lr_scheduler is not None:
+            ck["lr_schedulers"] = [self.lr_scheduler.state_dict()]      # Lightning's key
+        torch.save(ck, path)
 
     def _restore_model(self, ckpt_path):
         """Model part of a resume: BEFORE the executors / optimizer are built (they snapshot the weights)."""
@@ -162,6 +176,67 @@ class Trainer:
         st = (ck.get("optimizer_states") or [None])[0]
         if st is not None and hasattr(self.optimizer, "load_state_dict"):
             self.optimizer.load_state_dict(st)
+        saved = (ck.get("lr_schedulers") or [None])[0]
+        if self.lr_scheduler is not None and saved is not None:
+            self.lr_scheduler.load_state_dict(saved)      # the step count: the curve continues where the checkpoint left it
+
+    @staticmethod
+    def unpack_optimizers(ret):
+        """What `configure_optimizers()` returned -> (optimizer, scheduler or None).  One optimizer, at most one scheduler."""
+        opts, scheds = ret, []
+        if isinstance(ret, dict):
+            opts, scheds = ret["optimizer"], ret.get("lr_scheduler")
+        elif isinstance(ret, (list, tuple)) and len(ret) == 2 and all(isinstance(x, (list, tuple)) for x in ret):
+            opts, scheds = ret
+        opts = list(opts) if isinstance(opts, (list, tuple)) else [opts]
+        scheds = [] if scheds is None else list(scheds) if isinstance(scheds, (list, tuple)) else [scheds]
+        if len(opts) != 1 or len(scheds) > 1:
+            raise ValueError(f"configure_optimizers() returned {len(opts)} optimizers and {len(scheds)} schedulers: this loop "
+                             "drives one optimizer and at most one scheduler")
+        sched = scheds[0] if scheds else None
+        if isinstance(sched, dict):
+            interval, freq = sched.get("interval", "step"), int(sched.get("frequency", 1))
+            if interval != "step" or freq != 1:
+                raise ValueError(f"lr scheduler with interval='{interval}', frequency={freq}: the scheduler is stepped once per "
+                                 "optimizer step ('step', 1); a run is bounded by max_steps, not by epochs")
+            sched = sched["scheduler"]
+        return opts[0], sched
+
+    def _set_up_lr_schedule(self):
+        """Before the first step (and so before any capture): hand an engine optimizer the LambdaLR's curve as a device table."""
+        from torch.optim.lr_scheduler import LambdaLR
+        from ctrlora_amd.train import _FlatAdamW
+        sched = self.lr_scheduler
+        self._lr_on_device = False
+        if sched is None or not isinstance(self.optimizer, _FlatAdamW) or self.device.type != "cuda":
+            return
+        if isinstance(sched, LambdaLR):
+            from ctrlora_amd.lr_schedule import compile_lambda_lr
+            self.optimizer.set_lr_schedule(compile_lambda_lr(sched, self.max_steps))
+            self._lr_on_device = True
+        elif self.graph_step:
+            raise ValueError(f"graph_step refused: a {type(sched).__name__} moves the learning rate on the host, a copy to the "
+                             "device between replays that makes the host wait for the step before; only a LambdaLR is compiled "
+                             "to a device table")
+
+    def _lr_logs(self):
+        """The learning rate(s) of the host mirror, under `train/lr` or, with parameter groups, `train/lr/<group>`."""
+        groups = self.optimizer.param_groups
+        if len(groups) == 1:
+            return {"train/lr": float(groups[0]["lr"])}
+        return {f"train/lr/{g.get('name', k)}": float(g["lr"]) for k, g in enumerate(groups)}
+
+    def _step_lr(self, model, step, log):
+        """After optimizer step `step` (1-based): log the lr it used, then move the scheduler on to the next step's."""
+        if self.lr_scheduler is None:
+            return {}
+        logs = self._lr_logs() if log else {}
+        if log:
+            self.logged_lr.append((step, logs))
+        self.lr_scheduler.step()
+        if not self._lr_on_device and hasattr(self.optimizer, "sync_hyper"):
+            self.optimizer.sync_hyper()
+        return logs
 
     # ------------------------------------------------------------------ the loop
     def fit(self, model, train_dataloader, ckpt_path: Optional[str] = None):
@@ -177,11 +252,11 @@ class Trainer:
             model.set_engine_dtype(self.engine_dtype())
         ck = self._restore_model(ckpt_path) if ckpt_path else None
         self._init_distributed(model)
-        opt = model.configure_optimizers()
-        self.optimizer = opt[0] if isinstance(opt, (list, tuple)) else opt
+        self.optimizer, self.lr_scheduler = self.unpack_optimizers(model.configure_optimizers())
         if ck is not None:
             self._restore_optimizer(ck)
         self._set_up_grad_norm()
+        self._set_up_lr_schedule()
         if self.graph_step and self._norm_on and not self._norm_in_opt:
             raise ValueError(f"graph_step with gradient clipping needs an engine optimizer, not {type(self.optimizer).__name__}")
         if self.graph_step:
@@ -216,8 +291,10 @@ class Trainer:
                     self.optimizer.zero_grad()
                     self.global_step += 1
                     model.global_step = self.global_step
-                    if self.global_step % self.log_every_n_steps == 0:
-                        self._log_grad_norm(model, norm, self.global_step)
+                    log = self.global_step % self.log_every_n_steps == 0
+                    lr_logs = self._step_lr(model, self.global_step, log)
+                    if log:
+                        self._log_grad_norm(model, norm, self.global_step, more=lr_logs)
                     if self.is_global_zero and self.global_step % self.log_every_n_steps == 0:
                         self.logged.append((self.global_step, float(loss.detach())))
                         print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss.detach()):.5f}")
@@ -250,16 +327,17 @@ class Trainer:
         max_norm = self.gradient_clip_val if self.gradient_clip_val > 0.0 else float("inf")
         return torch.nn.utils.clip_grad_norm_(params, max_norm)
 
-    def _log_grad_norm(self, model, norm, step, extra=None):
-        """`train/grad_norm` of optimizer step `step` through the model's log_dict (with `extra`, or else with what the model
-        logged last): called at the steps where the loss is read on the host already."""
-        if norm is None:
-            return
-        norm = float(norm)
-        self.logged_grad_norm.append((step, norm))
-        if callable(getattr(model, "log_dict", None)):
+    def _log_grad_norm(self, model, norm, step, extra=None, more=None):
+        """`train/grad_norm` of optimizer step `step` (and `more`: the learning rates) through the model's log_dict (with `extra`,
+        or else with what the model logged last): called at the steps where the loss is read on the host already."""
+        more = dict(more or {})
+        if norm is not None:
+            norm = float(norm)
+            self.logged_grad_norm.append((step, norm))
+            more["train/grad_norm"] = norm
+        if more and callable(getattr(model, "log_dict", None)):
             prev = extra if extra is not None else getattr(model, "last_logged", None)
-            model.log_dict({**(prev if isinstance(prev, dict) else {}), "train/grad_norm": norm})
+            model.log_dict({**(prev if isinstance(prev, dict) else {}), **more})
 
     # ------------------------------------------------------------------ the loop, optimizer step as hipGraph replays
     def _make_graph_step(self, model, tensors):
@@ -321,8 +399,11 @@ class Trainer:
                 loss3 = loss3.clone()                   # a replay overwrites its output: callbacks may keep theirs
                 loss = loss3[2]
                 losses = {"train/loss_simple": loss3[0], "train/loss_vlb": loss3[1], "train/loss": loss}
-                if last and self._norm_in_opt and (self.global_step + 1) % self.log_every_n_steps == 0:
-                    self._log_grad_norm(model, self.optimizer.last_grad_norm()[0], self.global_step + 1, extra=losses)
+                log = last and (self.global_step + 1) % self.log_every_n_steps == 0
+                lr_logs = self._step_lr(model, self.global_step + 1, log) if last else {}
+                if log and (self._norm_in_opt or lr_logs):
+                    self._log_grad_norm(model, self.optimizer.last_grad_norm()[0] if self._norm_in_opt else None,
+                                        self.global_step + 1, extra=losses, more=lr_logs)
                 else:
                     model.log_dict(losses)
                 if last:

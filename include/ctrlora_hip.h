@@ -515,6 +515,29 @@ int cl_grad_norm(const float* const* bufs, const long* counts, int nbuf, const f
                  float* scratch, void* stream);
 int cl_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper, int* step, const float* clip,
                       void* stream);
+/* Parameter groups and a learning-rate schedule for cl_adamw_dev, on the device, added in ABI 7 (compatible).  Not in the
+ * reference's fine-tuning path (one group, constant lr); torch.optim.AdamW's param_groups and LambdaLR's indexing.
+ * cl_adamw_dev_groups: one AdamW launch over a flat fp32 buffer of n elements whose 64-float chunks belong to ngroups (1 .. 8)
+ * parameter groups.
+ *   hyper_table  fp32 [ngroups][6]: cl_adamw_dev's {lr, beta1, beta2, eps, weight_decay, grad_scale}, one row per group
+ *   chunk_group  uint8 [n / 64]: the group of elements [64 c, 64 c + 64).  An entry >= ngroups is clamped to ngroups - 1 in the
+ *                kernel, so nothing is read beyond the table; a caller should not rely on it.
+ *   step         the shared device counter, advanced with cl_tick before the launch; the bias corrections are per group
+ *   clip         NULL, or the out of cl_grad_norm: gi = g[i] * (hyper[5] * clip[1]) with the group's own hyper[5], the two
+ *                scalars multiplied first, as cl_adamw_dev_clip does
+ * Every element gets the expression of cl_adamw_dev (cl_adamw_dev_clip with clip) with its group's row: the same bits as that
+ * launch over the chunk's span with that row as hyper.  g, the table and the map are only read.  A wave reads and writes whole
+ * 256-byte chunks and looks the group up once per chunk: 28 + 1 / 64 bytes per element.
+ * Refused, before anything is launched: a null p / g / m / v / hyper_table / chunk_group / step, n <= 0, n not a multiple of
+ * 64, ngroups outside 1 .. 8.
+ * cl_lr_schedule: hyper_table[gidx][0] = lr_table[min(*step - 1, T - 1)][gidx] for every group, one small launch.  lr_table is
+ * fp32 [T][ngroups]; *step is the counter AFTER cl_tick, so optimizer step s (from 1) takes row s - 1 -- LambdaLR's indexing, the
+ * lambda at 0 feeds the first step -- and the last row holds past the end (a counter below 1 takes row 0).  Columns 1 .. 5 of
+ * the table are not touched.  Launch it after cl_tick and before the step's first AdamW launch.
+ * Refused, before anything is launched: a null hyper_table / lr_table / step, T < 1, ngroups outside 1 .. 8. */
+int cl_adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const float* hyper_table, int ngroups,
+                        const unsigned char* chunk_group, int* step, const float* clip, void* stream);
+int cl_lr_schedule(float* hyper_table, int ngroups, const float* lr_table, int T, const int* step, void* stream);
 /* Exponential moving average of trained weights on the device, added in ABI 7 (compatible): LitEma.forward
  * (ldm/modules/ema.py) for one flat fp32 buffer, with no host round trip, so that it replays inside a hipGraph.
  *   u = *num_updates (already advanced by cl_tick, like cl_adamw_dev's step)

@@ -65,7 +65,7 @@ class DDPM(_LightningFree):
                  cosine_s=8e-3, given_betas=None, original_elbo_weight=0., v_posterior=0., l_simple_weight=1.,
                  conditioning_key=None, parameterization="eps", scheduler_config=None, use_positional_encodings=False,
                  learn_logvar=False, logvar_init=0., make_it_fit=False, ucg_training=None, reset_ema=False,
-                 reset_num_ema_updates=False, ema_decay=0.9999, min_snr_gamma=0.0, huber_delta=1.0):
+                 reset_num_ema_updates=False, ema_decay=0.9999, min_snr_gamma=0.0, huber_delta=1.0, optim_groups=None):
         super().__init__()
         if parameterization != "eps" or learn_logvar:
             raise NotImplementedError("CtrLoRA configs: eps-parameterisation, fixed logvar")
@@ -81,6 +81,13 @@ class DDPM(_LightningFree):
         if not (np.isfinite(float(huber_delta)) and float(huber_delta) > 0.0):
             raise ValueError(f"huber_delta={huber_delta!r} must be finite and > 0")
         self.min_snr_gamma, self.huber_delta = float(min_snr_gamma), float(huber_delta)
+        # scheduler_config (ddpm.py:1288-1299 of the reference: the target's `.schedule` is a LambdaLR's lr_lambda) and
+        # optim_groups (not in the reference: rules that split the trained tensors into optimizer parameter groups) are acted on
+        # by ControlFinetuneLDM.configure_optimizers; the class that cannot honour them says so instead of dropping them
+        if self.refuses_lr_options and (scheduler_config is not None or optim_groups is not None):
+            raise NotImplementedError(f"scheduler_config / optim_groups: learning-rate schedules and parameter groups are built "
+                                      f"for fine-tuning only (ControlFinetuneLDM), not for {type(self).__name__}")
+        self.scheduler_config, self.optim_groups = scheduler_config, optim_groups
         self.parameterization, self.clip_denoised, self.log_every_t = parameterization, clip_denoised, log_every_t
         self.first_stage_key, self.image_size, self.channels = first_stage_key, image_size, channels
         self.model = DiffusionWrapper(unet_config, conditioning_key)
@@ -181,6 +188,7 @@ class DDPM(_LightningFree):
         return loss
 
     supports_ema = False      # ControlFinetuneLDM: True
+    refuses_lr_options = False      # ControlPretrainLDM: True
 
     @contextlib.contextmanager
     def ema_scope(self, context=None):

@@ -63,7 +63,67 @@ def get_parser():
                         "included; 0.9999 is its default), updated on the device inside every optimizer step and saved in the "
                         "checkpoints as model_ema.*; extract it with tool_extract_weights.py --ema; 0 = off (the default)")
     add_loss_args(p)
+    add_lr_args(p)
     return p
+
+
+def add_lr_args(p):
+    """Learning-rate schedule and optimizer parameter groups (fine-tuning only); all off by default.  The groups and the flags are
+    not in the reference; the scheduler takes the path of its LatentDiffusion.configure_optimizers (a LambdaLR per step)."""
+    p.add_argument("--lr_schedule", choices=("constant", "linear", "cosine"), default=None,
+                   help="move the learning rate along this curve over --max_steps (after --lr_warmup_steps of linear warm-up, "
+                        "down to --lr_min_ratio x --lr); the curve lives in device memory and is read inside the optimizer step, "
+                        "so it works under --graph without a copy between replays (default: a fixed learning rate)")
+    p.add_argument("--lr_warmup_steps", type=_non_negative_int, default=0,
+                   help="optimizer steps of linear warm-up, step n (from 0) at (n + 1) / N of the rate; alone it implies "
+                        "--lr_schedule constant")
+    p.add_argument("--lr_min_ratio", type=_unit_interval, default=0.0,
+                   help="where the linear and cosine curves end, as a fraction of --lr")
+    p.add_argument("--lora_plus_ratio", type=_positive_float, default=None,
+                   help="LoRA+: train the LoRA up matrices (lora_layer.up.) at this multiple of --lr, as a parameter group of "
+                        "their own inside the same fused AdamW launch (default: one learning rate)")
+    p.add_argument("--no_decay_norm_bias", action="store_true", default=False,
+                   help="no weight decay on the norm layers and the biases: a parameter group with weight_decay 0 (applied "
+                        "after the LoRA+ rule)")
+
+
+def _non_negative_int(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"{text}: a number of steps >= 0")
+    return value
+
+
+def _unit_interval(text):
+    value = float(text)
+    if not 0.0 <= value <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text}: a ratio in [0, 1]")
+    return value
+
+
+def _positive_float(text):
+    value = float(text)
+    if not value > 0.0 or value != value or value == float("inf"):
+        raise argparse.ArgumentTypeError(f"{text}: a finite ratio > 0")
+    return value
+
+
+def lr_model_params(max_steps, lr_schedule=None, lr_warmup_steps=0, lr_min_ratio=0.0, lora_plus_ratio=None,
+                    no_decay_norm_bias=False) -> dict:
+    """The flags of add_lr_args: what create_model overrides in the config's model.params; nothing at the defaults."""
+    out = {}
+    if lr_schedule is not None or lr_warmup_steps > 0:
+        out["scheduler_config"] = {"target": "ctrlora_amd.lr_schedule.WarmupDecay",
+                                   "params": {"kind": lr_schedule or "constant", "warmup_steps": int(lr_warmup_steps),
+                                              "total_steps": int(max_steps), "min_ratio": float(lr_min_ratio)}}
+    rules = []
+    if lora_plus_ratio is not None:
+        rules.append({"name": "lora_up", "match": ["lora_layer.up."], "lr_scale": float(lora_plus_ratio)})
+    if no_decay_norm_bias:
+        rules.append({"name": "no_decay", "match": ["norm", ".bias"], "weight_decay": 0.0})
+    if rules:
+        out["optim_groups"] = rules
+    return out
 
 
 def add_loss_args(p):
@@ -170,7 +230,10 @@ def main(argv=None):
         print("Gradient accumulation:", args.gradacc)
         print("Total batch size:", args.bs * world * args.gradacc)
     model = create_model(args.config, params={**ema_model_params(args.ema_decay),
-                                              **loss_model_params(args.min_snr_gamma, args.loss, args.huber_delta)}).cpu()
+                                              **loss_model_params(args.min_snr_gamma, args.loss, args.huber_delta),
+                                              **lr_model_params(args.max_steps, args.lr_schedule, args.lr_warmup_steps,
+                                                                args.lr_min_ratio, args.lora_plus_ratio,
+                                                                args.no_decay_norm_bias)}).cpu()
     model.learning_rate = args.lr
     model.sd_locked = True
     model.only_mid_control = False
