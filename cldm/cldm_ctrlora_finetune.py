@@ -187,6 +187,7 @@ class ControlFinetuneLDM(ControlLDM):
         land in the flat buffer the optimizer's parameters view.  `grad_scale` multiplies d loss / d eps (not the three
         returned scalars): 1 / accumulate_grad_batches under gradient accumulation, what `(loss / acc).backward()` does."""
         from ctrlora_amd import hip
+        from ctrlora_amd.train import p_losses_launch
         if self.loss_type not in hip.LOSS_KINDS or self.original_elbo_weight != 0.:
             raise NotImplementedError("engine_train_step: l2 loss without the elbo term (every CtrLoRA config)")
         x_noisy = self.q_sample(x_start=x_start, t=t, noise=noise)
@@ -197,16 +198,9 @@ class ControlFinetuneLDM(ControlLDM):
         eng = self.engine()
         eps = eng.forward(x_noisy, t, cond_txt, hints, control_scales=list(self.control_scales), record=True,
                           only_mid_control=self.only_mid_control)
-        out = torch.empty(3, dtype=torch.float32, device=eps.device)
-        scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
-        d_eps = torch.empty_like(eps)
-        if self.loss_weights is None and self.loss_type == "l2":
-            hip.p_losses_mse(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
-                             float(grad_scale), float(self.l_simple_weight), 0.0)
-        else:       # a per-timestep weight table (min_snr_gamma / set_loss_weights) and / or the Huber loss
-            hip.p_losses_w(eps, noise.float().contiguous(), d_eps, t.long().contiguous(), self.lvlb_weights, out, scratch,
-                           float(grad_scale), float(self.l_simple_weight), 0.0, wt=self.loss_weights,
-                           kind=hip.LOSS_KINDS[self.loss_type], delta=self.huber_delta)
+        # with a per-timestep weight table (min_snr_gamma / set_loss_weights) and / or the Huber loss: cl_p_losses_w
+        out, d_eps = p_losses_launch(eps, noise, t, self.lvlb_weights, grad_scale, self.l_simple_weight, 0.0, wt=self.loss_weights,
+                                     kind=hip.LOSS_KINDS[self.loss_type], delta=self.huber_delta)
         if torch.cuda.is_current_stream_capturing():
             self.loss_weights_pinned = True       # the graph holds the table's address, or the kernel that has none
         eng.backward(d_eps)

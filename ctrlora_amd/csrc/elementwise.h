@@ -10,17 +10,18 @@ namespace cl {
 // head bytes, bit 1 = tail bytes, aux = 16-byte vectors; vit_patch_rows: 1 = float2 (PAIR) loads; mse_loss: aux = workgroups;
 // transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
 // qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel; grad_norm: the partial
-// launch's grid, aux = buffers; plosses: form 0 = cl_p_losses_mse, 4 | kind << 1 | (table given) = cl_p_losses_w; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar.
+// launch's grid, aux = buffers; plosses: form 0 = cl_p_losses_mse, 4 | kind << 1 | (table given) = cl_p_losses_w; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar;
+// adamw_dev_groups: form 1 = with a clip coefficient, aux = groups; lr_schedule: aux = groups.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
   EW_ADAMW_DEV, EW_DDIM_SET_T, EW_DDIM_STEP_DEV, EW_DPMPP_STEP, EW_DPMPP_STEP_DEV, EW_DPM_SET_T, EW_ADAMW, EW_POOL2X2,
   EW_COLSUM, EW_REPACK, EW_PACK2D, EW_VIT_PATCH_ROWS, EW_VIT_TOKENS,
   EW_CLIP_TEXT_EMBED, EW_GATHER_ROWS, EW_POSTERIOR_PAIR, EW_PLMS_STEP, EW_PLMS_STEP_DEV,
-  EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP
+  EW_QSAMPLE_BLEND, EW_GRAD_NORM, EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP,
+  EW_ADAMW_DEV_GROUPS, EW_LR_SCHEDULE
 };
-// appended after EW_SWAP (41): adamw_dev_groups: form 1 = with a clip coefficient, aux = groups; lr_schedule: aux = groups
-enum { EW_ADAMW_DEV_GROUPS = EW_SWAP + 1, EW_LR_SCHEDULE };
+static_assert(EW_SWAP == 41 && EW_LR_SCHEDULE == 43, "the ids are read by number through cl_debug_ew_last_launch: append only");
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
   int dtype;     // CL_BF16 / CL_F32 of the typed launchers (transpose: the output's), -1 where there is no dtype argument

@@ -361,57 +361,17 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- p_losses reduction (ddpm.py:902-918)
-// Deterministic (no float atomics): block (chunk, b) reduces one slice of sample b into scratch[b][chunk] and
-// writes d_eps; the finishing block sums the slices in a fixed order:
-//   out[0] = loss_simple = mean_b mean((eps-target)^2)          (logvar == 0)
-//   out[1] = loss_vlb    = mean_b lvlb[t_b] * mean((eps-target)^2)
-//   out[2] = loss        = l_simple_weight * loss_simple + elbo_weight * loss_vlb
-constexpr int PL_CHUNKS = 16;
-__global__ __launch_bounds__(256) void plosses_partial_kernel(const float* __restrict__ eps,
-                                                              const float* __restrict__ target,
-                                                              float* __restrict__ d_eps, float* __restrict__ scratch,
-                                                              long per, float gmul) {
-  __shared__ float red[4];
-  const int b = blockIdx.y, chunk = blockIdx.x;
-  const long base = (long)b * per;
-  const long c0 = per * chunk / PL_CHUNKS, c1 = per * (chunk + 1) / PL_CHUNKS;
-  float acc = 0.f;
-  for (long i = c0 + threadIdx.x; i < c1; i += 256) {
-    const float d = eps[base + i] - target[base + i];
-    acc += d * d;
-    if (d_eps) d_eps[base + i] = d * gmul;
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) scratch[b * PL_CHUNKS + chunk] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-__global__ __launch_bounds__(64) void plosses_finish_kernel(const float* __restrict__ scratch, const long* __restrict__ t,
-                                                            const float* __restrict__ lvlb, float* __restrict__ out,
-                                                            float* __restrict__ per_sample, int B, long per,
-                                                            float w_simple, float w_elbo) {
-  if (threadIdx.x != 0) return;
-  float ls = 0.f, lv = 0.f;
-  for (int b = 0; b < B; ++b) {
-    float s = 0.f;
-    for (int c = 0; c < PL_CHUNKS; ++c) s += scratch[b * PL_CHUNKS + c];
-    s /= (float)per;
-    if (per_sample) per_sample[b] = s;
-    ls += s;
-    if (lvlb) lv += lvlb[t[b]] * s;
-  }
-  ls /= (float)B; lv /= (float)B;
-  out[0] = ls; out[1] = lv; out[2] = w_simple * ls + w_elbo * lv;
-}
-
-// The same reduction with a per-timestep weight and a choice of rho (cl_p_losses_w), in the geometry and summation order of the
-// two kernels above.  The launcher sends what those two already compute to them: l2 without a table to the partial kernel above,
-// any call without a table to the finishing kernel above (the per-sample means are unweighted either way).
+// Deterministic (no float atomics): block (chunk, b) reduces one slice of sample b into scratch[b][chunk] and writes d_eps; the
+// finishing block sums the slices in a fixed order.  One kernel pair serves cl_p_losses_mse (l2, no table) and cl_p_losses_w (a
+// per-timestep weight table `wt`, NULL = weight 1, and a choice of rho):
 //   KIND 0 (l2)     rho(d) = d^2,                                                   rho'(d) = 2 d   (the 2 is in gmul)
 //   KIND 1 (Huber)  rho(d) = |d| <= delta ? d^2 / 2 : delta (|d| - delta / 2),      rho'(d) = clamp(d, -delta, delta)
 //   l_b = mean rho(d) of sample b (unweighted: scratch, per_sample, out[0], out[1]);  d_eps = rho'(d) * gmul * wt[t_b]
-//   out[2] = w_simple * mean_b (wt[t_b] l_b) + w_elbo * out[1]
+//   out[0] = loss_simple = mean_b l_b                              (logvar == 0)
+//   out[1] = loss_vlb    = mean_b lvlb[t_b] * l_b
+//   out[2] = loss        = w_simple * mean_b (wt[t_b] l_b) + w_elbo * out[1]
 // t and wt are read on the device, once per workgroup: a captured launch follows both.
+constexpr int PL_CHUNKS = 16;
 template <int KIND>
 __global__ __launch_bounds__(256) void plosses_w_partial_kernel(const float* __restrict__ eps,
                                                                 const float* __restrict__ target,
@@ -453,9 +413,10 @@ __global__ __launch_bounds__(64) void plosses_w_finish_kernel(const float* __res
     if (per_sample) per_sample[b] = s;
     ls += s;
     if (lvlb) lv += lvlb[t[b]] * s;
-    lw += wt[t[b]] * s;
+    if (wt) lw += wt[t[b]] * s;
   }
   ls /= (float)B; lv /= (float)B; lw /= (float)B;
+  if (!wt) lw = ls;               // weight 1: the weighted mean is the plain one, summed once
   out[0] = ls; out[1] = lv; out[2] = w_simple * lw + w_elbo * lv;
 }
 
@@ -487,17 +448,35 @@ __global__ void ddim_step_kernel(const float* x, const float* __restrict__ e_c, 
 }
 
 // ---------------------------------------------------------------- fused AdamW over one flat fp32 buffer
-// torch.optim.AdamW defaults (cldm_ctrlora_finetune.py:105): decoupled decay, bias correction.
+// torch.optim.AdamW defaults (cldm_ctrlora_finetune.py:105): decoupled decay, bias correction.  The update is written once:
+// adam_group() derives a step's scalars from {lr, beta1, beta2, eps, weight_decay, grad_scale} and the step count, adam_elem()
+// updates one element, and every AdamW entry point runs its elements through them.  Contraction is off in both and the two
+// operations that are fused are written as fmaf, so the bits are stated here and not left to the compiler's heuristics --
+//     1 - lr wd           = fma(-lr, wd, 1)
+//     m' = b1 m + (1 - b1) gi = fma(1 - b1, gi, b1 m)
+//     v' = b2 v + ((1 - b2) gi) gi,  p' = (1 - lr wd) p - ((lr / bc1) m') / (sqrt(v') / bc2_sqrt + eps):  every operation rounded
+// (tests/golden/step_bits.pt holds every entry point to the bits it had when each kernel carried its own copy of the expression).
+struct AdamGroup { float decay, beta1, omb1, beta2, omb2, bc2_sqrt, eps, lr_bc1, gscale; };
+__host__ __device__ inline AdamGroup adam_group(float lr, float beta1, float beta2, float eps, float wd, float gscale, float st) {
+#pragma clang fp contract(off)
+  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
+  return AdamGroup{__builtin_fmaf(-lr, wd, 1.0f), beta1, 1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, lr / bc1, gscale};
+}
+__device__ __forceinline__ void adam_elem(const AdamGroup& h, float& pi, float g, float& mi, float& vi) {
+#pragma clang fp contract(off)
+  const float gi = g * h.gscale;
+  const float pd = pi * h.decay;
+  mi = __builtin_fmaf(h.omb1, gi, h.beta1 * mi);
+  vi = h.beta2 * vi + h.omb2 * gi * gi;
+  const float denom = sqrtf(vi) / h.bc2_sqrt + h.eps;
+  pi = pd - h.lr_bc1 * mi / denom;
+}
+// cl_adamw: the scalars by value, the bias corrections formed on the host (the launcher builds `h`)
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, long n, float lr, float beta1, float beta2, float eps,
-                             float wd, float bc1, float bc2_sqrt, float gscale) {
+                             float* __restrict__ v, long n, const AdamGroup h) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * mi / denom;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(h, pi, g[i], mi, vi);
     p[i] = pi; m[i] = mi; v[i] = vi;
   }
 }
@@ -506,24 +485,6 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // A captured graph replays the SAME kernel arguments, so anything that changes from step to step must
 // live in device memory: the optimizer step count / hyper-parameters and the DDIM loop cursor.
 __global__ void tick_kernel(int* c) { *c += 1; }
-
-// hyper = {lr, beta1, beta2, eps, weight_decay, grad_scale}; *step was already incremented for this step
-__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, const float* __restrict__ hyper,
-                                 const int* __restrict__ step) {
-  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
-  const float st = (float)*step;
-  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * mi / denom;
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
 
 // ---------------------------------------------------------------- global gradient norm + clip coefficient
 // torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite=False) over up to GN_MAX_BUFS flat fp32 buffers, in two
@@ -590,80 +551,45 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
   out[0] = norm; out[1] = coef;
 }
 
-// adamw_dev_kernel on the clipped gradient: gi = g[i] * (grad_scale * coef), clip = grad_norm_finish_kernel's out.  The two
-// scalars are multiplied FIRST: with coef == 1.0f the product is grad_scale itself and every bit equals adamw_dev_kernel's.
-__global__ void adamw_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                      float* __restrict__ v, long n, const float* __restrict__ hyper,
-                                      const int* __restrict__ step, const float* __restrict__ clip) {
-  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5] * clip[1];
-  const float st = (float)*step;
-  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * mi / denom;
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
-// ---------------------------------------------------------------- AdamW with parameter groups, learning rates from a device table
-// adamw_dev_kernel / adamw_dev_clip_kernel over one flat buffer whose 64-float chunks belong to up to AG_MAX_GROUPS groups:
-// table = [ngroups][6] rows of cl_adamw_dev's hyper, chunk_group[c] = the group of elements [64 c, 64 c + 64).  The flat buffers
-// align every tensor to 64 floats (packing.TrainableSet.materialize), so a chunk never holds two tensors.  A wave owns one chunk
-// per trip: its 64 lanes read and write one whole 256-byte line of each of the four streams, exactly the access of the
-// one-group kernels (lane = consecutive float), and the group is ONE byte load per wave and trip (all lanes read the same address,
-// made wave-uniform with readfirstlane) -- 1 / 64 byte per element next to the 28 the streams move.  The first `ngroups` threads of
-// a workgroup derive the group's scalars once (the bias corrections from the shared step counter, the same powf / sqrtf on the
-// same operands as the one-group kernels) and leave them in LDS.  An entry >= ngroups is clamped to the last group: nothing is
-// read beyond the table.
-// The bits are those of adamw_dev_kernel / adamw_dev_clip_kernel over the chunk with the group's row as `hyper`.  Those two are
-// compiled with hipcc's default contraction, which fuses two of their operations and no other; this kernel states that outcome
-// instead of leaving it to the optimizer (with the scalars in LDS it fuses a third): contraction is off here and the two fused
-// operations are written as fmaf --
-//     1 - lr wd           = fma(-lr, wd, 1)
-//     m' = b1 m + (1 - b1) gi = fma(1 - b1, gi, b1 m)
-//     v' = b2 v + ((1 - b2) gi) gi,  p' = (1 - lr wd) p - ((lr / bc1) m') / (sqrt(v') / bc2_sqrt + eps):  every operation rounded
-// tests/test_gpu_optim_groups.py holds the two families to each other bit for bit, so a compiler that contracts the one-group
-// kernels differently shows there.
+// ---------------------------------------------------------------- AdamW from device-resident state, with parameter groups
+// One kernel behind cl_adamw_dev, cl_adamw_dev_clip and cl_adamw_dev_groups.  table = [ngroups][6] rows of {lr, beta1, beta2, eps,
+// weight_decay, grad_scale} (a one-group launch passes its `hyper` as a table of one row), *step was already incremented for this
+// step, clip = grad_norm_finish_kernel's out or NULL: gi = g[i] * (grad_scale * coef), the two scalars multiplied FIRST, so a
+// coefficient of 1.0f gives the bits of no clipping.  chunk_group[c] = the group of elements [64 c, 64 c + 64), or NULL: every
+// chunk is group 0.  The flat buffers align every tensor to 64 floats (packing.TrainableSet.materialize), so a chunk never holds
+// two tensors.  A wave owns one chunk per trip: its 64 lanes read and write one whole 256-byte line of each of the four streams
+// (lane = consecutive float; with 256 threads that is element blockIdx * 256 + tid and a stride of gridDim * 256, a grid-stride
+// loop over elements), and the group is ONE byte load per wave and trip (all lanes read the same address, made wave-uniform with
+// readfirstlane) -- 1 / 64 byte per element next to the 28 the streams move.  The first `ngroups` threads of a workgroup derive
+// their group's scalars once and leave them in LDS.  An entry >= ngroups is clamped to the last group: nothing is read beyond the
+// table.  The last chunk may be ragged (n % 64 != 0, one-group launches only): lanes at or beyond n do nothing.
 constexpr int AG_MAX_GROUPS = 8;
-struct AdamGroup { float decay, beta1, omb1, beta2, omb2, bc2_sqrt, eps, lr_bc1, gscale; };
-__device__ __forceinline__ AdamGroup adam_group(const float* __restrict__ hyper, float st, const float* __restrict__ clip) {
-#pragma clang fp contract(off)
-  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float gscale = clip ? hyper[5] * clip[1] : hyper[5];
-  const float bc1 = 1.0f - powf(beta1, st), bc2_sqrt = sqrtf(1.0f - powf(beta2, st));
-  return AdamGroup{__builtin_fmaf(-lr, wd, 1.0f), beta1, 1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, lr / bc1, gscale};
-}
-__device__ __forceinline__ void adam_elem(const AdamGroup& h, float& pi, float g, float& mi, float& vi) {
-#pragma clang fp contract(off)
-  const float gi = g * h.gscale;
-  const float pd = pi * h.decay;
-  mi = __builtin_fmaf(h.omb1, gi, h.beta1 * mi);
-  vi = h.beta2 * vi + h.omb2 * gi * gi;
-  const float denom = sqrtf(vi) / h.bc2_sqrt + h.eps;
-  pi = pd - h.lr_bc1 * mi / denom;
-}
-__global__ __launch_bounds__(256) void adamw_dev_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v, long nchunks,
-                                                               const float* __restrict__ table, int ngroups,
-                                                               const unsigned char* __restrict__ chunk_group,
-                                                               const int* __restrict__ step, const float* __restrict__ clip) {
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, long n,
+                                                        const float* __restrict__ table, int ngroups,
+                                                        const unsigned char* __restrict__ chunk_group,
+                                                        const int* __restrict__ step, const float* __restrict__ clip) {
   __shared__ AdamGroup hp[AG_MAX_GROUPS];
-  if ((int)threadIdx.x < ngroups) hp[threadIdx.x] = adam_group(table + 6 * threadIdx.x, (float)*step, clip);
+  if ((int)threadIdx.x < ngroups) {
+    const float* __restrict__ h = table + 6 * threadIdx.x;
+    hp[threadIdx.x] = adam_group(h[0], h[1], h[2], h[3], h[4], clip ? h[5] * clip[1] : h[5], (float)*step);
+  }
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
-  for (long c = wave; c < nchunks; c += nwaves) {
-    int grp = __builtin_amdgcn_readfirstlane((int)chunk_group[c]);
-    grp = grp < ngroups ? grp : ngroups - 1;
+  for (long c = wave; (c << 6) < n; c += nwaves) {
+    int grp = 0;
+    if (chunk_group) {
+      grp = __builtin_amdgcn_readfirstlane((int)chunk_group[c]);
+      grp = grp < ngroups ? grp : ngroups - 1;
+    }
     const AdamGroup h = hp[grp];
     const long i = (c << 6) + lane;
-    float pi = p[i], mi = m[i], vi = v[i];
-    adam_elem(h, pi, g[i], mi, vi);
-    p[i] = pi; m[i] = mi; v[i] = vi;
+    if (i < n) {
+      float pi = p[i], mi = m[i], vi = v[i];
+      adam_elem(h, pi, g[i], mi, vi);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+    }
   }
 }
 
@@ -1288,10 +1214,8 @@ int adamw(float* p, const float* g, float* m, float* v, long n, float lr, float 
           float wd, int step, float gscale, hipStream_t st) {
   ew_rec_begin();
   if (n < 0 || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2 = 1.0f - powf(beta2, (float)step);
   const dim3 grid(ew_grid(n));
-  hipLaunchKernelGGL(adamw_kernel, grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), gscale);
+  hipLaunchKernelGGL(adamw_kernel, grid, dim3(256), 0, st, p, g, m, v, n, adam_group(lr, beta1, beta2, eps, wd, gscale, (float)step));
   return ew_done(EW_ADAMW, -1, grid, 256);
 }
 int plosses_mse(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
@@ -1303,8 +1227,8 @@ int plosses_mse(const float* eps, const float* target, float* d_eps, const long*
   // d loss / d eps with loss = w_simple * mean(...) (the elbo term is not differentiated: weight 0 in every config)
   const float gmul = 2.0f * gscale * w_simple / ((float)per * (float)B);
   const dim3 grid(PL_CHUNKS, B);
-  hipLaunchKernelGGL(plosses_partial_kernel, grid, dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
-  hipLaunchKernelGGL(plosses_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, out, per_sample, B, per, w_simple, w_elbo);
+  hipLaunchKernelGGL((plosses_w_partial_kernel<0>), grid, dim3(256), 0, st, eps, target, d_eps, scratch, t, nullptr, per, gmul, 0.f);
+  hipLaunchKernelGGL(plosses_w_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, nullptr, out, per_sample, B, per, w_simple, w_elbo);
   return ew_done(EW_PLOSSES, -1, grid, 256);
 }
 int plosses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, const float* wt, float* out,
@@ -1318,11 +1242,9 @@ int plosses_w(const float* eps, const float* target, float* d_eps, const long* t
   // rho' carries the 2 of l2 here; the table's factor is applied on the device (elementwise.hip: plosses_w_partial_kernel)
   const float gmul = (kind == 0 ? 2.0f : 1.0f) * gscale * w_simple / ((float)per * (float)B);
   const dim3 grid(PL_CHUNKS, B);
-  if (kind == 1) hipLaunchKernelGGL((plosses_w_partial_kernel<1>), grid, dim3(256), 0, st, eps, target, d_eps, scratch, t, wt, per, gmul, delta);
-  else if (wt) hipLaunchKernelGGL((plosses_w_partial_kernel<0>), grid, dim3(256), 0, st, eps, target, d_eps, scratch, t, wt, per, gmul, 0.f);
-  else hipLaunchKernelGGL(plosses_partial_kernel, grid, dim3(256), 0, st, eps, target, d_eps, scratch, per, gmul);
-  if (wt) hipLaunchKernelGGL(plosses_w_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, wt, out, per_sample, B, per, w_simple, w_elbo);
-  else hipLaunchKernelGGL(plosses_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, out, per_sample, B, per, w_simple, w_elbo);
+  hipLaunchKernelGGL((kind == 1 ? plosses_w_partial_kernel<1> : plosses_w_partial_kernel<0>), grid, dim3(256), 0, st, eps, target, d_eps,
+                     scratch, t, wt, per, gmul, delta);
+  hipLaunchKernelGGL(plosses_w_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, wt, out, per_sample, B, per, w_simple, w_elbo);
   return ew_done(EW_PLOSSES, -1, grid, 256, 4 | (kind << 1) | (wt ? 1 : 0));
 }
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
@@ -1380,7 +1302,7 @@ int adamw_dev(float* p, const float* g, float* m, float* v, long n, const float*
   ew_rec_begin();
   if (n < 0 || !hyper || !step || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
   const dim3 grid(ew_grid(n));
-  hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step);
+  hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, 1, nullptr, step, nullptr);
   return ew_done(EW_ADAMW_DEV, -1, grid, 256);
 }
 long grad_norm_scratch_floats(int nbuf) {
@@ -1412,7 +1334,7 @@ int adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const f
   ew_rec_begin();
   if (n < 0 || !hyper || !step || !clip || (n > 0 && (!p || !g || !m || !v))) return CL_EINVAL;
   const dim3 grid(ew_grid(n));
-  hipLaunchKernelGGL(adamw_dev_clip_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, step, clip);
+  hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper, 1, nullptr, step, clip);
   return ew_done(EW_ADAMW_DEV_CLIP, -1, grid, 256);
 }
 int adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const float* hyper_table, int ngroups,
@@ -1421,8 +1343,7 @@ int adamw_dev_groups(float* p, const float* g, float* m, float* v, long n, const
   if (!p || !g || !m || !v || !hyper_table || !chunk_group || !step) return CL_EINVAL;      // clip may be NULL: no clipping
   if (n <= 0 || n % 64 != 0 || ngroups < 1 || ngroups > AG_MAX_GROUPS) return CL_EINVAL;
   const dim3 grid(ew_grid(n));                 // a wave per 64-float chunk and trip: n / 64 chunks over 4 waves a workgroup
-  hipLaunchKernelGGL(adamw_dev_groups_kernel, grid, dim3(256), 0, st, p, g, m, v, n / 64, hyper_table, ngroups, chunk_group, step,
-                     clip);
+  hipLaunchKernelGGL(adamw_dev_kernel, grid, dim3(256), 0, st, p, g, m, v, n, hyper_table, ngroups, chunk_group, step, clip);
   return ew_done(EW_ADAMW_DEV_GROUPS, -1, grid, 256, clip ? 1 : 0, ngroups);
 }
 int lr_schedule(float* hyper_table, int ngroups, const float* lr_table, int T, const int* step, hipStream_t st) {

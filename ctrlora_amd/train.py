@@ -69,25 +69,33 @@ class ApplyModelFn(torch.autograd.Function):
         return (None,) * 10
 
 
+def p_losses_launch(eps, target, t, lvlb, grad_scale, w_simple, w_elbo, wt=None, kind=0, delta=1.0):
+    """The p_losses reduction of one step, for PLossFn and engine_train_step: allocates the 3-vector {loss_simple, loss_vlb,
+    loss}, the kernels' scratch (16 floats per sample) and d loss / d eps (times `grad_scale`), and launches cl_p_losses_mse
+    when there is no weight table and the loss is l2, cl_p_losses_w otherwise.  `eps` is fp32 and contiguous.  Returns
+    (out, d_eps)."""
+    target, t = target.float().contiguous(), t.long().contiguous()
+    out = torch.empty(3, dtype=torch.float32, device=eps.device)
+    scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
+    d_eps = torch.empty_like(eps)
+    if wt is None and kind == 0:
+        hip.p_losses_mse(eps, target, d_eps, t, lvlb, out, scratch, float(grad_scale), float(w_simple), float(w_elbo))
+    else:
+        hip.p_losses_w(eps, target, d_eps, t, lvlb, out, scratch, float(grad_scale), float(w_simple), float(w_elbo),
+                       wt=wt, kind=kind, delta=delta)
+    return out, d_eps
+
+
 class PLossFn(torch.autograd.Function):
     """LatentDiffusion.p_losses' reduction (ddpm.py:902-918 with logvar = 0) as ONE deterministic HIP reduction:
     returns the 3-vector {loss_simple, loss_vlb, loss = w_simple * loss_simple + w_elbo * loss_vlb} and keeps
     d(w_simple * loss_simple) / d eps for the backward (the elbo term is not differentiated; its weight is 0 in
     every CtrLoRA config and the caller checks that).  `wt` (a per-timestep weight table, e.g. Min-SNR-gamma) and `kind` 1
-    (Huber with `delta`) go through cl_p_losses_w; without either the call is cl_p_losses_mse, as before."""
+    (Huber with `delta`) go through cl_p_losses_w; without either the call is cl_p_losses_mse (p_losses_launch)."""
 
     @staticmethod
     def forward(ctx, eps, target, t, lvlb, w_simple, w_elbo, wt=None, kind=0, delta=1.0):
-        eps = eps.float().contiguous()
-        target = target.float().contiguous()
-        out = torch.empty(3, dtype=torch.float32, device=eps.device)
-        scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
-        d_eps = torch.empty_like(eps)
-        if wt is None and kind == 0:
-            hip.p_losses_mse(eps, target, d_eps, t.long().contiguous(), lvlb, out, scratch, 1.0, float(w_simple), float(w_elbo))
-        else:
-            hip.p_losses_w(eps, target, d_eps, t.long().contiguous(), lvlb, out, scratch, 1.0, float(w_simple), float(w_elbo),
-                           wt=wt, kind=kind, delta=delta)
+        out, d_eps = p_losses_launch(eps.float().contiguous(), target, t, lvlb, 1.0, w_simple, w_elbo, wt, kind, delta)
         ctx.save_for_backward(d_eps)
         return out
 
@@ -343,6 +351,17 @@ class _FlatAdamW(torch.optim.Optimizer):
         hip.grad_norm(bufs, self._hyper, self._max_norm, self.grad_norm_out, self._norm_scratch)
         return True
 
+    def _adamw(self, flat, grad, st, step, clip, chunk_group=None):
+        """The update of ONE flat buffer with the state `st` and the device counter `step`: the one place that picks the entry
+        point -- a chunk map: cl_adamw_dev_groups, else `clip` (what `_grad_norm()` returned): cl_adamw_dev_clip, else
+        cl_adamw_dev."""
+        if chunk_group is not None:
+            hip.adamw_dev_groups(flat, grad, st.m, st.v, self._hyper_table, chunk_group, step, self.grad_norm_out if clip else None)
+        elif clip:
+            hip.adamw_dev_clip(flat, grad, st.m, st.v, self._hyper, step, self.grad_norm_out)
+        else:
+            hip.adamw_dev(flat, grad, st.m, st.v, self._hyper, step)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
@@ -446,13 +465,8 @@ class FusedAdamW(_FlatAdamW):
         if ema is not None and ema.use_num_updates:
             hip.tick(ema.num_updates)     # LitEma counts before it averages; without the warm-up the count stays at -1
         for k, (ex, st) in enumerate(zip(self.executors, self._states)):
-            if self._chunk_group is not None:
-                hip.adamw_dev_groups(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper_table, self._chunk_group[k],
-                                     self._step_dev, self.grad_norm_out if clip else None)
-            elif clip:
-                hip.adamw_dev_clip(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev, self.grad_norm_out)
-            else:
-                hip.adamw_dev(ex.tr.flat, ex.tr.flat_grad, st.m, st.v, self._hyper, self._step_dev)
+            self._adamw(ex.tr.flat, ex.tr.flat_grad, st, self._step_dev, clip,
+                        self._chunk_group[k] if self._chunk_group is not None else None)
             if ema is not None:
                 hip.ema_update(self._ema_flats[k], ex.tr.flat, ema.decay, ema.num_updates)
             ex.repack()
@@ -515,10 +529,7 @@ class PretrainAdamW(_FlatAdamW):
         clip = self._grad_norm([ts.flat_grad for ts, _ in sets])
         for ts, st in sets:
             hip.tick(st.step)
-            if clip:
-                hip.adamw_dev_clip(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step, self.grad_norm_out)
-            else:
-                hip.adamw_dev(ts.flat, ts.flat_grad, st.m, st.v, self._hyper, st.step)
+            self._adamw(ts.flat, ts.flat_grad, st, st.step, clip)
         self.executor.repack()
 
     def zero_grad(self, set_to_none: bool = False):

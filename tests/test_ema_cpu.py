@@ -386,7 +386,11 @@ def test_symbols_are_declared_with_the_signatures_hip_binds():
     doc = hdr[:hdr.index("int cl_ema_update")]
     assert "added in ABI 7 (compatible)" in doc[doc.rindex("/*"):], "the additions are marked compatible where they are declared"
     ew = open(os.path.join(ROOT, "ctrlora_amd", "csrc", "elementwise.h")).read().replace("\n", " ")
-    assert "EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP };" in " ".join(ew.split()), "new records are appended, none renumbered"
+    ew = " ".join(ew.split())
+    assert "EW_ADAMW_DEV_CLIP, EW_EMA_UPDATE, EW_SWAP, EW_ADAMW_DEV_GROUPS, EW_LR_SCHEDULE };" in ew, "new records are appended, none renumbered"
+    ids = [s.split("=")[0].strip() for s in ew[ew.index("enum {") + 6:ew.index("};")].split(",")]
+    assert ids[0] == "EW_GEGLU_FWD" and ids.index("EW_ADAMW_DEV_CLIP") + 1 == 39 and ids.index("EW_EMA_UPDATE") + 1 == 40 and \
+        ids.index("EW_SWAP") + 1 == 41, "one enum counted from 1: the numbers cl_debug_ew_last_launch reports"
 
 
 def test_abi_is_still_7_and_host_side_refusals_launch_nothing():

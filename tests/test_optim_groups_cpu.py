@@ -383,8 +383,11 @@ def test_symbols_are_declared_with_the_signatures_hip_binds():
     doc = doc[doc.rindex("/*"):]
     assert "added in ABI 7 (compatible)" in doc and "Refused" in doc and "clamped" in doc
     ew = " ".join(open(os.path.join(ROOT, "ctrlora_amd", "csrc", "elementwise.h")).read().split())
-    assert "EW_EMA_UPDATE, EW_SWAP };" in ew and "enum { EW_ADAMW_DEV_GROUPS = EW_SWAP + 1, EW_LR_SCHEDULE };" in ew, \
+    assert "EW_EMA_UPDATE, EW_SWAP, EW_ADAMW_DEV_GROUPS, EW_LR_SCHEDULE };" in ew and ew.count("enum {") == 1, \
         "new records are appended, none renumbered"
+    ids = [s.split("=")[0].strip() for s in ew[ew.index("enum {") + 6:ew.index("};")].split(",")]
+    assert "EW_GEGLU_FWD = 1" in ew and ids.index("EW_SWAP") + 1 == 41 and ids.index("EW_ADAMW_DEV_GROUPS") + 1 == 42 and \
+        ids.index("EW_LR_SCHEDULE") + 1 == 43 == len(ids), "the numbers tests/test_gpu_optim_groups.py reads the records by"
 
 
 def test_host_side_refusals_launch_nothing():
