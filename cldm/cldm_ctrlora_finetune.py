@@ -200,13 +200,43 @@ class ControlFinetuneLDM(ControlLDM):
                           only_mid_control=self.only_mid_control)
         # with a per-timestep weight table (min_snr_gamma / set_loss_weights) and / or the Huber loss: cl_p_losses_w
         out, d_eps = p_losses_launch(eps, noise, t, self.lvlb_weights, grad_scale, self.l_simple_weight, 0.0, wt=self.loss_weights,
-                                     kind=hip.LOSS_KINDS[self.loss_type], delta=self.huber_delta)
+                                     kind=hip.LOSS_KINDS[self.loss_type], delta=self.huber_delta, bands=self.train_loss_bands)
         if torch.cuda.is_current_stream_capturing():
             self.loss_weights_pinned = True       # the graph holds the table's address, or the kernel that has none
         eng.backward(d_eps)
         if self.dp is not None:
             self.dp.on_backward_done()
         return out
+
+    @torch.no_grad()
+    def engine_eval_step(self, x_start, cond, t, noise, acc, n_valid=None):
+        """One forward-only validation step (ctrlora_amd.validation; not in the reference): q_sample, the engine forward
+        without recording, the plain l2 reduction without d loss / d eps and without per-timestep weights (cl_p_losses_mse,
+        whatever the training objective is), and cl_loss_bands adding the per-sample losses to `acc` (device fp64
+        [nbands + 1][3]).  `n_valid`: None or a device int32, the leading samples that count (a padded batch).  Every launch
+        is one of this library's kernels, so the step is capturable; it leaves the recorded forward of a training step, the
+        gradient buffers and `loss_weights_pinned` alone.  Returns the per-sample losses (device fp32 [B])."""
+        from ctrlora_amd import hip
+        t = t.long().contiguous()
+        noise = noise.float().contiguous()
+        x_noisy = self.q_sample(x_start=x_start, t=t, noise=noise)
+        cc = cond["c_crossattn"]
+        cond_txt = cc[0] if len(cc) == 1 else torch.cat(cc, 1)
+        hints = [self._hint_latent(cond)]
+        if not torch.cuda.is_current_stream_capturing():
+            self._sync_trainables()
+        eng = self.engine()
+        # the text context changes from batch to batch: the context K / V cache of the samplers must stay off
+        assert not eng.cache_context_kv, "engine_eval_step inside a sampler's context_kv scope"
+        eps = eng.forward(x_noisy, t, cond_txt, hints, control_scales=list(self.control_scales), record=False,
+                          only_mid_control=self.only_mid_control)
+        B = eps.shape[0]
+        out = torch.empty(3, dtype=torch.float32, device=eps.device)
+        scratch = torch.empty(16 * B, dtype=torch.float32, device=eps.device)
+        per = torch.empty(B, dtype=torch.float32, device=eps.device)
+        hip.p_losses_mse(eps, noise, None, t, None, out, scratch, 1.0, 1.0, 0.0, per_sample=per)
+        hip.loss_bands(per, t, self.num_timesteps, acc.shape[0] - 1, acc, n_valid=n_valid)
+        return per
 
     def trainable_names(self):
         """Name filter of :84-108 (LoRA layers; zero convs incl. middle_block_out; `norm` layers)."""

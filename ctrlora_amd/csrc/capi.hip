@@ -353,6 +353,7 @@ int cl_adamw(float* p, const float* g, float* m, float* v, long n, float lr, flo
 
 int cl_p_losses_mse(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out, float* per_sample, float* scratch, int B, long per_sample_elems, float gscale, float w_simple, float w_elbo, void* stream) { return plosses_mse(eps, target, d_eps, t, lvlb, out, per_sample, scratch, B, per_sample_elems, gscale, w_simple, w_elbo, S(stream)); }
 int cl_p_losses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out, float* per_sample, float* scratch, int B, long per_sample_elems, float gscale, float w_simple, float w_elbo, const float* wt, int kind, float delta, void* stream) { return plosses_w(eps, target, d_eps, t, lvlb, wt, out, per_sample, scratch, B, per_sample_elems, kind, delta, gscale, w_simple, w_elbo, S(stream)); }
+int cl_loss_bands(const float* per_sample, const long* t, int B, int T, int nbands, const int* n_valid, double* acc, void* stream) { return loss_bands(per_sample, t, B, T, nbands, n_valid, acc, S(stream)); }
 int cl_conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout, int C, int tap, int stride, int pad, void* stream) { return conv_tap_gather(dtype, x, ldx, out, ldo, B, Hin, Win, Hout, Wout, C, tap, stride, pad, S(stream)); }
 int cl_softmax_rows(int dtype, const float* Sm, long lds_, void* P, long ldp, long M, int N, float scale, void* stream) { return softmax_rows(dtype, Sm, lds_, P, ldp, M, N, scale, S(stream)); }
 int cl_zero(void* p, long nbytes, void* stream) { return zero_bytes(p, nbytes, S(stream)); }

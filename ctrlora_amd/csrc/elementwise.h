@@ -11,7 +11,8 @@ namespace cl {
 // transpose: form = the input's dtype; plms_step: form = phase; posterior_sample_pair: form 1 = 16-byte loads and stores, 0 = scalar, aux = tensors (1 or 2);
 // qsample_blend: form as posterior_sample_pair, aux bit 0 = mask per sample, bit 1 = mask per channel; grad_norm: the partial
 // launch's grid, aux = buffers; plosses: form 0 = cl_p_losses_mse, 4 | kind << 1 | (table given) = cl_p_losses_w; ema_update / swap: form 1 = 16-byte accesses with scalar head and tail (aux = vectors), 0 = scalar;
-// adamw_dev_groups: form 1 = with a clip coefficient, aux = groups; lr_schedule: aux = groups.
+// adamw_dev_groups: form 1 = with a clip coefficient, aux = groups; lr_schedule: aux = groups; loss_bands: form 1 = with n_valid,
+// aux = bands.
 enum {
   EW_GEGLU_FWD = 1, EW_GEGLU_BWD, EW_SILU_FWD, EW_SILU_BWD, EW_AXPBY, EW_TRANSPOSE, EW_NCHW_TO_TOK, EW_TOK_TO_NCHW,
   EW_TIMESTEP, EW_TIMESTEP_F, EW_QSAMPLE, EW_MSE, EW_PLOSSES, EW_ZERO, EW_CONV_TAP, EW_SOFTMAX, EW_DDIM_STEP, EW_TICK,
@@ -22,6 +23,8 @@ enum {
   EW_ADAMW_DEV_GROUPS, EW_LR_SCHEDULE
 };
 static_assert(EW_SWAP == 41 && EW_LR_SCHEDULE == 43, "the ids are read by number through cl_debug_ew_last_launch: append only");
+// the enumeration is closed at 43 (the tests of the step pin its last member): later records continue the numbering as constants
+constexpr int EW_LOSS_BANDS = 44;
 struct EwLaunchRec {
   int id;        // EW_* of the entry point, 0 = nothing launched
   int dtype;     // CL_BF16 / CL_F32 of the typed launchers (transpose: the output's), -1 where there is no dtype argument
@@ -60,6 +63,10 @@ int plosses_mse(const float* eps, const float* target, float* d_eps, const long*
 int plosses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, const float* wt, float* out,
               float* per_sample, float* scratch, int B, long per, int kind, float delta, float gscale, float w_simple,
               float w_elbo, hipStream_t st);
+// {count, sum, sum of squares} of the per-sample losses by timestep band, added to a device double [nbands + 1][3] in index
+// order by one workgroup (elementwise.hip)
+int loss_bands(const float* per_sample, const long* t, int B, int T, int nbands, const int* n_valid, double* acc,
+               hipStream_t st);
 int zero_bytes(void* p, long nbytes, hipStream_t st);
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
                     int C, int tap, int stride, int pad, hipStream_t st);

@@ -420,6 +420,48 @@ __global__ __launch_bounds__(64) void plosses_w_finish_kernel(const float* __res
   out[0] = ls; out[1] = lv; out[2] = w_simple * lw + w_elbo * lv;
 }
 
+// ---------------------------------------------------------------- per-sample losses by timestep band (not in the reference)
+// acc = double [nbands + 1][3] = {count, sum, sum of squares} per band, row nbands = all samples; the launch ADDS to it.
+//   band(t) = min(clamp(t, 0, T - 1) * nbands / T, nbands - 1)   (64-bit integers)
+// One workgroup: the samples are staged LB_CHUNK at a time in LDS (their band and their loss), then thread r < nbands walks
+// the chunk in index order for row r and thread nbands for the total row, each in fp64 registers -- no atomics, one writer per
+// row, the bits of the sequential loop.  A non-finite loss reaches its own band and the total only.  *n_valid (optional) is
+// read on the device, so a captured launch follows it.
+constexpr int LB_CHUNK = 1024, LB_THREADS = 128;
+__global__ __launch_bounds__(LB_THREADS) void loss_bands_kernel(const float* __restrict__ per_sample, const long* __restrict__ t,
+                                                                int B, int T, int nbands, const int* __restrict__ n_valid,
+                                                                double* __restrict__ acc) {
+  __shared__ float loss_s[LB_CHUNK];
+  __shared__ unsigned char band_s[LB_CHUNK];
+  int nv = B;
+  if (n_valid) { nv = *n_valid; nv = nv < 0 ? 0 : nv > B ? B : nv; }
+  const int row = threadIdx.x;
+  const bool owner = row <= nbands;
+  double cnt = 0.0, s1 = 0.0, s2 = 0.0;
+  if (owner) { cnt = acc[row * 3 + 0]; s1 = acc[row * 3 + 1]; s2 = acc[row * 3 + 2]; }
+  for (int c0 = 0; c0 < nv; c0 += LB_CHUNK) {
+    const int n = nv - c0 < LB_CHUNK ? nv - c0 : LB_CHUNK;
+    for (int i = threadIdx.x; i < n; i += LB_THREADS) {
+      long tt = t[c0 + i];
+      tt = tt < 0 ? 0 : tt > T - 1 ? T - 1 : tt;
+      const long k = tt * nbands / T;
+      band_s[i] = (unsigned char)(k < nbands - 1 ? k : nbands - 1);
+      loss_s[i] = per_sample[c0 + i];
+    }
+    __syncthreads();
+    if (owner) {
+      for (int i = 0; i < n; ++i) {
+        if (row == nbands || band_s[i] == row) {
+          const double x = (double)loss_s[i];
+          cnt += 1.0; s1 += x; s2 += x * x;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (owner) { acc[row * 3 + 0] = cnt; acc[row * 3 + 1] = s1; acc[row * 3 + 2] = s2; }
+}
+
 // ---------------------------------------------------------------- DDIM update (ddim_hacked.py:192,203-231)
 // coef = device table [S][4] = {a_t, a_prev, sigma_t, sqrt(1 - a_t)} (fp32), row `index` is used.  x_prev may alias x
 // (element-wise), so neither is __restrict__.  One body for the host-index and the device-cursor launch (below): an eager
@@ -1246,6 +1288,14 @@ int plosses_w(const float* eps, const float* target, float* d_eps, const long* t
                      scratch, t, wt, per, gmul, delta);
   hipLaunchKernelGGL(plosses_w_finish_kernel, dim3(1), dim3(64), 0, st, scratch, t, lvlb, wt, out, per_sample, B, per, w_simple, w_elbo);
   return ew_done(EW_PLOSSES, -1, grid, 256, 4 | (kind << 1) | (wt ? 1 : 0));
+}
+int loss_bands(const float* per_sample, const long* t, int B, int T, int nbands, const int* n_valid, double* acc,
+               hipStream_t st) {
+  ew_rec_begin();
+  if (!per_sample || !t || !acc || (reinterpret_cast<uintptr_t>(acc) & 7)) return CL_EINVAL;
+  if (B < 1 || B > 65535 || T < 1 || nbands < 1 || nbands > 64 || nbands > T) return CL_EINVAL;
+  hipLaunchKernelGGL(loss_bands_kernel, dim3(1), dim3(LB_THREADS), 0, st, per_sample, t, B, T, nbands, n_valid, acc);
+  return ew_done(EW_LOSS_BANDS, -1, dim3(1), LB_THREADS, n_valid ? 1 : 0, nbands);
 }
 int conv_tap_gather(int dtype, const void* x, long ldx, void* out, long ldo, int B, int Hin, int Win, int Hout, int Wout,
                     int C, int tap, int stride, int pad, hipStream_t st) {

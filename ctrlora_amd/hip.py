@@ -110,6 +110,7 @@ _SIGS = {
     "cl_mse_loss": [_P, _P, _P, _P, _L, _F, _P],
     "cl_p_losses_mse": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P],
     "cl_p_losses_w": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _P, _I, _F, _P],
+    "cl_loss_bands": [_P, _P, _I, _I, _I, _P, _P, _P],
     "cl_zero": [_P, _L, _P],
     "cl_softmax_rows": [_I, _P, _L, _P, _L, _L, _I, _F, _P],
     "cl_conv_tap_gather": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -792,6 +793,18 @@ def p_losses_w(eps, target, d_eps, t, lvlb, out3, scratch, gscale=1.0, w_simple=
                              scratch.data_ptr(), B, eps.numel() // B, gscale, w_simple, w_elbo, ptr(wt), int(kind), float(delta),
                              stream()), "cl_p_losses_w")
     return out3
+
+
+def loss_bands(per_sample, t, T, nbands, acc, n_valid=None):
+    """acc (fp64 [nbands + 1][3]: count, sum, sum of squares per timestep band, last row = all) += the fp32 per-sample losses at
+    timesteps t (int64); n_valid: None or a device int32, the first clamp(n_valid, 0, B) samples count (cl_loss_bands)."""
+    B = per_sample.numel()
+    assert per_sample.dtype == torch.float32 and per_sample.is_contiguous() and t.dtype == torch.int64 and t.is_contiguous()
+    assert t.numel() == B and acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == 3 * (nbands + 1)
+    assert n_valid is None or (n_valid.dtype == torch.int32 and n_valid.numel() == 1)
+    _chk(lib().cl_loss_bands(per_sample.data_ptr(), t.data_ptr(), B, int(T), int(nbands), ptr(n_valid), acc.data_ptr(), stream()),
+         "cl_loss_bands")
+    return acc
 
 
 def conv_tap_gather(x, out, B, Hin, Win, Hout, Wout, tap, stride, pad):

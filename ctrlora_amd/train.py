@@ -69,21 +69,42 @@ class ApplyModelFn(torch.autograd.Function):
         return (None,) * 10
 
 
-def p_losses_launch(eps, target, t, lvlb, grad_scale, w_simple, w_elbo, wt=None, kind=0, delta=1.0):
+def p_losses_launch(eps, target, t, lvlb, grad_scale, w_simple, w_elbo, wt=None, kind=0, delta=1.0, bands=None):
     """The p_losses reduction of one step, for PLossFn and engine_train_step: allocates the 3-vector {loss_simple, loss_vlb,
     loss}, the kernels' scratch (16 floats per sample) and d loss / d eps (times `grad_scale`), and launches cl_p_losses_mse
     when there is no weight table and the loss is l2, cl_p_losses_w otherwise.  `eps` is fp32 and contiguous.  Returns
-    (out, d_eps)."""
+    (out, d_eps).  `bands` (None = the launches above and nothing else): a `LossBands` whose table takes the step's per-sample
+    losses by timestep band, one cl_loss_bands launch more."""
     target, t = target.float().contiguous(), t.long().contiguous()
     out = torch.empty(3, dtype=torch.float32, device=eps.device)
     scratch = torch.empty(16 * eps.shape[0], dtype=torch.float32, device=eps.device)
     d_eps = torch.empty_like(eps)
+    per = None if bands is None else torch.empty(eps.shape[0], dtype=torch.float32, device=eps.device)
     if wt is None and kind == 0:
-        hip.p_losses_mse(eps, target, d_eps, t, lvlb, out, scratch, float(grad_scale), float(w_simple), float(w_elbo))
+        hip.p_losses_mse(eps, target, d_eps, t, lvlb, out, scratch, float(grad_scale), float(w_simple), float(w_elbo), per_sample=per)
     else:
         hip.p_losses_w(eps, target, d_eps, t, lvlb, out, scratch, float(grad_scale), float(w_simple), float(w_elbo),
-                       wt=wt, kind=kind, delta=delta)
+                       per_sample=per, wt=wt, kind=kind, delta=delta)
+    if bands is not None:
+        hip.loss_bands(per, t, bands.num_timesteps, bands.nbands, bands.acc)
+        bands.last = (per, t)
     return out, d_eps
+
+
+class LossBands:
+    """Training-side telemetry (Trainer(loss_bands=N)): a device fp64 table [nbands + 1][3] that every p_losses launch of a
+    training step adds its per-sample losses to (cl_loss_bands), inside the captured step where there is one.  `last` = the
+    (per_sample, t) device tensors of the latest launch; after a replay they hold that replay's values.  Rank-local."""
+
+    def __init__(self, num_timesteps, nbands, device):
+        self.num_timesteps, self.nbands = int(num_timesteps), int(nbands)
+        self.acc = hip.zero_(torch.empty(self.nbands + 1, 3, dtype=torch.float64, device=device))
+        self.last = None
+
+    def read_and_clear(self):
+        tab = self.acc.cpu()
+        hip.zero_(self.acc)
+        return tab
 
 
 class PLossFn(torch.autograd.Function):
@@ -94,15 +115,15 @@ class PLossFn(torch.autograd.Function):
     (Huber with `delta`) go through cl_p_losses_w; without either the call is cl_p_losses_mse (p_losses_launch)."""
 
     @staticmethod
-    def forward(ctx, eps, target, t, lvlb, w_simple, w_elbo, wt=None, kind=0, delta=1.0):
-        out, d_eps = p_losses_launch(eps.float().contiguous(), target, t, lvlb, 1.0, w_simple, w_elbo, wt, kind, delta)
+    def forward(ctx, eps, target, t, lvlb, w_simple, w_elbo, wt=None, kind=0, delta=1.0, bands=None):
+        out, d_eps = p_losses_launch(eps.float().contiguous(), target, t, lvlb, 1.0, w_simple, w_elbo, wt, kind, delta, bands)
         ctx.save_for_backward(d_eps)
         return out
 
     @staticmethod
     def backward(ctx, g):
         (d_eps,) = ctx.saved_tensors
-        return d_eps * g[2], None, None, None, None, None, None, None, None
+        return d_eps * g[2], None, None, None, None, None, None, None, None, None
 
 
 class _AdamState:

@@ -29,6 +29,12 @@ lr on the host (`scheduler.step()` + `sync_hyper()`), which `graph_step` refuses
 
 `graph_step=True` (LoRA fine-tuning on a GPU only; off by default) replays the optimizer step as hipGraphs
 (`ctrlora_amd.train.GraphedTrainStep`) instead of launching its ~1900 kernels one by one: see `Trainer._fit_graphed`.
+
+Validation (`fit(..., val_dataloaders=)` with `val_check_interval=N` optimizer steps; off by default; `ctrlora_amd.validation`):
+a fixed plan of (sample, t, noise) triples, the plain l2 loss by timestep band in a small fp64 table filled on the device
+(`cl_loss_bands`), read once per run; `val_ema` repeats the run inside `ema_scope()`, `save_best` writes `best.ckpt` on
+improvement, `limit_val_batches` caps a run.  A run forks every generator it draws on: training continues on the numbers it
+would have had.  `loss_bands=K` breaks the training loss down the same way, inside the step, rank-local.  See `Trainer._validate`.
 """
 from __future__ import annotations
 
@@ -64,12 +70,39 @@ def graph_step_refusal(model) -> Optional[str]:
     return None
 
 
+def validation_refusal(model) -> Optional[str]:
+    """Why this model cannot be validated / banded by the Trainer, in one line, or None."""
+    cm = getattr(model, "control_model", None)
+    if callable(getattr(model, "init_data_parallel", None)) or hasattr(cm, "switch_lora"):
+        return ("multi-task pre-training has one LoRA bank per task and no held-out set per bank: validation and loss bands are "
+                "built for fine-tuning only (ControlFinetuneLDM)")
+    return None
+
+
 class Trainer:
     def __init__(self, max_steps: int = 100000, accumulate_grad_batches: int = 1, precision=32,
                  callbacks: Sequence = (), default_root_dir: str = "runs/default", device: Optional[str] = None,
                  strategy: str = "ddp", accelerator: str = "gpu", devices=-1, log_every_n_steps: int = 50,
-                 graph_step=False, gradient_clip_val=None, gradient_clip_algorithm: str = "norm", track_grad_norm=-1):
+                 graph_step=False, gradient_clip_val=None, gradient_clip_algorithm: str = "norm", track_grad_norm=-1,
+                 val_check_interval: int = 0, limit_val_batches: Optional[int] = None, val_plan=None, val_ema: bool = False,
+                 save_best: bool = False, loss_bands: int = 0):
         self.max_steps = int(max_steps)
+        if int(val_check_interval) < 0:
+            raise ValueError(f"val_check_interval={val_check_interval!r} counts optimizer steps: >= 0 (0 = off)")
+        if limit_val_batches is not None and int(limit_val_batches) < 1:
+            raise ValueError(f"limit_val_batches={limit_val_batches!r} must be None (all) or >= 1")
+        if not 0 <= int(loss_bands) <= 64:
+            raise ValueError(f"loss_bands={loss_bands!r} must lie in 0 .. 64 (0 = off)")
+        self.val_check_interval = int(val_check_interval)
+        self.limit_val_batches = None if limit_val_batches is None else int(limit_val_batches)
+        self.val_plan, self.val_ema, self.save_best, self.loss_bands = val_plan, bool(val_ema), bool(save_best), int(loss_bands)
+        self.logged_val = []            # (global_step, {"val/loss_simple": ..., "val/loss_simple/t0-99": ..., ...}) per validation run
+        self.logged_train_bands = []    # (global_step, fp64 table [loss_bands + 1][3] of the interval) at log_every_n_steps
+        self.best_val = float("inf")    # the monitored validation loss of best.ckpt (save_best)
+        self.val_tables = None          # the fp64 tables of the latest run: [1 or 2 (live, EMA)][nbands + 1][3], reduced over ranks
+        self._val_loader = self._val_step = self._train_bands = None
+        self._val_on = self._val_on_engine = False
+        self._val_last_step = -1
         if gradient_clip_algorithm != "norm":
             raise ValueError(f"gradient_clip_algorithm='{gradient_clip_algorithm}' is not supported: gradients are clipped by their "
                              "global L2 norm only ('norm'); clipping by value is not offered")
@@ -239,8 +272,9 @@ class Trainer:
         return logs
 
     # ------------------------------------------------------------------ the loop
-    def fit(self, model, train_dataloader, ckpt_path: Optional[str] = None):
+    def fit(self, model, train_dataloader, ckpt_path: Optional[str] = None, val_dataloaders=None):
         self.model = model
+        self._check_validation_options(model, val_dataloaders)
         if self.graph_step:
             why = graph_step_refusal(model)
             if why is not None:
@@ -259,8 +293,21 @@ class Trainer:
         self._set_up_lr_schedule()
         if self.graph_step and self._norm_on and not self._norm_in_opt:
             raise ValueError(f"graph_step with gradient clipping needs an engine optimizer, not {type(self.optimizer).__name__}")
-        if self.graph_step:
-            return self._fit_graphed(model, train_dataloader)
+        self._set_up_validation(model, val_dataloaders)
+        try:
+            if self.graph_step:
+                self._fit_graphed(model, train_dataloader)
+            else:
+                self._fit_eager(model, train_dataloader)
+            if self._val_on and self._val_last_step != self.global_step:
+                self._validate(model)           # once at the end of fit, unless the last step's own run was it
+        finally:
+            if self._train_bands is not None:
+                model.train_loss_bands = None
+        self._call("on_train_end", model)
+        return self
+
+    def _fit_eager(self, model, train_dataloader):
         acc = self.accumulate_grad_batches
         dp = getattr(model, "dp", None)
         # an EMA of the trained weights (model.model_ema: ldm.modules.ema.ModelEma) that the optimizer does not carry inside its
@@ -298,6 +345,7 @@ class Trainer:
                     if self.is_global_zero and self.global_step % self.log_every_n_steps == 0:
                         self.logged.append((self.global_step, float(loss.detach())))
                         print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss.detach()):.5f}")
+                    self._after_optimizer_step(model)
                 self._call("on_train_batch_end", model, {"loss": loss.detach()}, batch, batch_idx)
                 self._call("on_batch_end", model)
                 if self.global_step >= self.max_steps:
@@ -306,8 +354,6 @@ class Trainer:
                 raise RuntimeError("empty dataloader")
             self.current_epoch += 1
             model.current_epoch = self.current_epoch
-        self._call("on_train_end", model)
-        return self
 
     # ------------------------------------------------------------------ gradient norm: clip and / or track
     def _set_up_grad_norm(self):
@@ -418,6 +464,7 @@ class Trainer:
                     if self.is_global_zero and self.global_step % self.log_every_n_steps == 0:
                         self.logged.append((self.global_step, float(loss)))
                         print(f"[trainer] step {self.global_step} epoch {self.current_epoch} loss {float(loss):.5f}")
+                    self._after_optimizer_step(model)
                 self._call("on_train_batch_end", model, {"loss": loss}, batch, batch_idx)
                 self._call("on_batch_end", model)
                 if self.global_step >= self.max_steps:
@@ -426,5 +473,111 @@ class Trainer:
                 raise RuntimeError("empty dataloader")
             self.current_epoch += 1
             model.current_epoch = self.current_epoch
-        self._call("on_train_end", model)
-        return self
+
+    # ------------------------------------------------------------------ validation by timestep band; training-side bands
+    def _check_validation_options(self, model, val_dataloaders):
+        """The refusals, before anything is built or moved."""
+        if self.val_check_interval > 0 and val_dataloaders is None:
+            raise ValueError(f"val_check_interval={self.val_check_interval} without val_dataloaders: there is nothing to validate on")
+        wants = (self.val_check_interval > 0 and val_dataloaders is not None) or self.loss_bands > 0
+        why = validation_refusal(model) if wants else None
+        if why is not None:
+            raise ValueError("validation / loss_bands refused: " + why)
+        if self.val_ema and getattr(model, "model_ema", None) is None:
+            raise ValueError("val_ema without an EMA of the trained weights (use_ema / --ema_decay): there is no second set of "
+                             "weights to validate")
+        if (self.val_ema or self.save_best) and not (self.val_check_interval > 0 and val_dataloaders is not None):
+            raise ValueError("val_ema / save_best need validation: val_check_interval > 0 and val_dataloaders")
+
+    def _set_up_validation(self, model, val_dataloaders):
+        """After the optimizer exists: which path a validation run takes, the plan, the training-side band table."""
+        from ctrlora_amd import validation as V
+        from ctrlora_amd.train import _FlatAdamW
+        engine_opt = isinstance(self.optimizer, _FlatAdamW) and self.device.type == "cuda"
+        self._val_on = self.val_check_interval > 0 and val_dataloaders is not None
+        self._val_loader, self._val_step, self._val_last_step = val_dataloaders, None, -1
+        if self._val_on:
+            if isinstance(val_dataloaders, (list, tuple)) and val_dataloaders and hasattr(val_dataloaders[0], "dataset"):
+                if len(val_dataloaders) != 1:
+                    raise ValueError(f"{len(val_dataloaders)} validation dataloaders: this loop validates on one set")
+                self._val_loader = val_dataloaders[0]
+            if self.val_plan is None:
+                self.val_plan = V.ValPlan(model.num_timesteps)
+            if self.val_plan.num_timesteps != model.num_timesteps:
+                raise ValueError(f"val_plan is laid out for {self.val_plan.num_timesteps} timesteps, the model has {model.num_timesteps}")
+            # the engine path (cl_loss_bands behind engine_eval_step) needs the engine's optimizer to own the weights; any other
+            # set-up runs the same loop through apply_model and the host restatement
+            self._val_on_engine = engine_opt and V.engine_eval_refusal(model, self.device) is None
+            if self._val_on_engine and self.graph_step:
+                self._val_step = V.GraphedEvalStep(model, self.val_plan.nbands)
+        self._train_bands = None
+        if self.loss_bands > 0:
+            if not engine_opt or not hasattr(type(model), "train_loss_bands"):
+                raise ValueError("loss_bands refused: the table is filled by the engine's loss kernels inside the training step (a "
+                                 "GPU, an engine optimizer and a model with p_losses on the engine)")
+            from ctrlora_amd.train import LossBands
+            self._train_bands = model.train_loss_bands = LossBands(model.num_timesteps, self.loss_bands, self.device)
+
+    def _after_optimizer_step(self, model):
+        """Right after optimizer step `global_step` was counted and logged: the interval's training bands, a validation run."""
+        if self._train_bands is not None and self.global_step % self.log_every_n_steps == 0:
+            self._log_train_bands(model)
+        if self._val_on and self.global_step % self.val_check_interval == 0:
+            self._validate(model)
+
+    def _log_train_bands(self, model):
+        """`train/loss_simple/t{lo}-{hi}`: the mean of this rank's per-sample training losses per timestep band since the last
+        read (rank-local: no exchange), read and cleared where the loss is read on the host already."""
+        from ctrlora_amd import validation as V
+        tab = self._train_bands.read_and_clear()
+        self.logged_train_bands.append((self.global_step, tab))
+        labels = [f"t{lo}-{hi}" for lo, hi in V.band_ranges(self._train_bands.num_timesteps, self._train_bands.nbands)]
+        logs = {f"train/loss_simple/{lab}": float(row[1] / row[0]) for lab, row in zip(labels, tab) if float(row[0]) > 0}
+        if callable(getattr(model, "log_dict", None)):
+            prev = getattr(model, "last_logged", None)
+            model.log_dict({**(prev if isinstance(prev, dict) else {}), **logs})
+        return logs
+
+    def _validate(self, model):
+        """One validation run (ctrlora_amd.validation): the live weights, with val_ema the EMA weights inside ema_scope() into a
+        second table; the tables are exchanged over the ranks and read ONCE; logged through model.log_dict, into `logged_val`
+        and as one JSON line of <log_dir>/val_log.jsonl; with save_best, best.ckpt when the monitored loss improved."""
+        from ctrlora_amd import validation as V
+        plan = self.val_plan
+        self._call("on_validation_start", model)
+        kw = dict(step=self._val_step, limit_batches=self.limit_val_batches, rank=self.global_rank, world=self.world_size,
+                  on_engine=self._val_on_engine, device=self.device)
+        tabs = [V.run_validation(model, self._val_loader, plan, **kw)]
+        if self.val_ema:
+            with model.ema_scope():
+                tabs.append(V.run_validation(model, self._val_loader, plan, **kw))
+        both = torch.stack(tabs)
+        if self.world_size > 1:
+            import torch.distributed as dist
+            if dist.get_backend() == "nccl":
+                both = both.to(self.device)
+            both = V.reduce_tables(both, self.world_size)
+        both = both.cpu()                      # the one read of a run
+        self.val_tables = both
+        logs = V.table_logs(both[0], plan)
+        if self.val_ema:
+            logs.update(V.table_logs(both[1], plan, suffix="_ema"))
+        self._val_last_step = self.global_step
+        self.logged_val.append((self.global_step, logs))
+        if callable(getattr(model, "log_dict", None)):
+            model.log_dict(logs)
+        if self.is_global_zero:
+            import math
+            row = {"global_step": self.global_step, "epoch": self.current_epoch}
+            row.update({k: (v if math.isfinite(v) else None) for k, v in logs.items()})
+            V.append_jsonl(os.path.join(self.log_dir, "val_log.jsonl"), row)
+            print(f"[trainer] step {self.global_step} val/loss_simple {logs['val/loss_simple']:.5f} "
+                  f"+- {logs['val/loss_simple_se']:.5f}" +
+                  (f"  ema {logs['val/loss_simple_ema']:.5f}" if self.val_ema else ""))
+        if self.save_best:
+            monitored = logs["val/loss_simple_ema" if self.val_ema else "val/loss_simple"]
+            if monitored < self.best_val:
+                self.best_val = monitored
+                self.save_checkpoint(os.path.join(self.checkpoint_callback.dirpath, "best.ckpt"))
+        self._call("on_validation_end", model)
+        return logs

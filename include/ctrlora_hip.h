@@ -474,6 +474,19 @@ int cl_p_losses_mse(const float* eps, const float* target, float* d_eps, const l
 int cl_p_losses_w(const float* eps, const float* target, float* d_eps, const long* t, const float* lvlb, float* out,
                   float* per_sample, float* scratch, int B, long per_sample_elems, float gscale, float w_simple,
                   float w_elbo, const float* wt, int kind, float delta, void* stream);
+/* The per-sample losses of a p_losses call broken down by timestep band, added in ABI 7 (compatible).  Not in the reference
+ * (its validation_step, ddpm.py:457-463, logs one mean at random t):
+ *   acc = device double [nbands + 1][3], row k = {count, sum, sum of squares} of band k, row nbands = of all samples
+ *   band(t) = min(clamp(t, 0, T - 1) * nbands / T, nbands - 1)     (64-bit integer arithmetic)
+ * The launch ADDS to what acc holds (clear it with cl_zero).  n_valid = NULL: all B samples count; else a device int, read on
+ * the device: the first clamp(*n_valid, 0, B) samples count (a ragged last batch padded to a captured shape replays unchanged).
+ * Sums and squares are formed in fp64 from the fp32 loss and added in index order within each row by one workgroup: no
+ * atomics, no waiting, no host synchronisation, no allocation; the bits of the sequential fp64 loop on every launch and
+ * replay.  A non-finite per_sample[b] reaches its own band's row and the total row only.
+ * Refused before anything is launched: a null per_sample / t / acc, B outside 1 .. 65535, T < 1, nbands outside
+ * 1 .. min(T, 64), acc not 8-byte aligned. */
+int cl_loss_bands(const float* per_sample, const long* t, int B, int T, int nbands, const int* n_valid, double* acc,
+                  void* stream);
 /* optimizer.zero_grad() / accumulator clears without an ATen launch: a fill KERNEL on `stream` (not hipMemsetAsync: memset
    nodes of small buffers were mis-ordered when a step is replayed as several consecutive hipGraphs) */
 int cl_zero(void* p, long nbytes, void* stream);

@@ -187,6 +187,24 @@ class DDPM(_LightningFree):
         self.log_dict(loss_dict)
         return loss
 
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """ddpm.py:457-463 of the reference: shared_step on the live weights and again inside ema_scope(), the second set of
+        keys with the suffix `_ema`, through log_dict; in eval() (so the keys are `val/*`: p_losses) and without gradients.
+        t and the noise are drawn as the reference draws them, at random: the fixed plan is ctrlora_amd.validation."""
+        was_training = self.training
+        self.eval()
+        try:
+            _, logs = self.shared_step(batch)
+            with self.ema_scope():
+                _, logs_ema = self.shared_step(batch)
+        finally:
+            self.train(was_training)
+        logs = {**logs, **{k + "_ema": v for k, v in logs_ema.items()}}
+        self.log_dict(logs)
+        return logs
+
+    train_loss_bands = None      # ctrlora_amd.train.LossBands while Trainer(loss_bands=N) runs
     supports_ema = False      # ControlFinetuneLDM: True
     refuses_lr_options = False      # ControlPretrainLDM: True
 
@@ -290,8 +308,10 @@ class LatentDiffusion(DDPM):
             # the three logged scalars come out of one deterministic HIP reduction
             from ctrlora_amd.train import PLossFn
             # (no table and l2: PLossFn launches cl_p_losses_mse, as before; otherwise cl_p_losses_w)
+            # train_loss_bands (Trainer(loss_bands=N); None = off): the training step's per-sample losses by timestep band
+            bands = self.train_loss_bands if self.training else None
             out = PLossFn.apply(model_output, target, t, self.lvlb_weights, self.l_simple_weight, 0.0, self.loss_weights,
-                                int(self.loss_type == "huber"), self.huber_delta)
+                                int(self.loss_type == "huber"), self.huber_delta, bands)
             loss = out[2]
             return loss, {f"{prefix}/loss_simple": out[0].detach(), f"{prefix}/loss_vlb": out[1].detach(),
                           f"{prefix}/loss": loss.detach()}

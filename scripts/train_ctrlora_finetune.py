@@ -64,7 +64,61 @@ def get_parser():
                         "checkpoints as model_ema.*; extract it with tool_extract_weights.py --ema; 0 = off (the default)")
     add_loss_args(p)
     add_lr_args(p)
+    add_val_args(p)
     return p
+
+
+def add_val_args(p):
+    """Held-out validation by timestep band and the training-side bands (ctrlora_amd.validation; fine-tuning only); all off by
+    default.  None of the flags is in the reference, whose validation_step draws t at random."""
+    p.add_argument("--val_dataroot", type=str, default=None,
+                   help="a held-out dataset laid out like --dataroot (CustomDataset); read in order, with prompt drop-out off")
+    p.add_argument("--val_latent_cache", type=str, default=None,
+                   help="directory written by scripts/tool_cache_latents.py for --val_dataroot: validate from the stored "
+                        "first-stage posteriors")
+    p.add_argument("--val_every", type=_non_negative_int, default=0,
+                   help="run validation every N optimizer steps and once at the end: a fixed set of (image, t, noise) triples, "
+                        "the plain l2 loss as val/loss_simple with its standard error and per timestep band, on the device "
+                        "(replayed as one hipGraph per batch under --graph), logged to val_log.jsonl; 0 = off (the default)")
+    p.add_argument("--val_batches", type=_non_negative_int, default=0, help="validate on the first M batches only; 0 = all")
+    p.add_argument("--val_bands", type=int, default=10, help="timestep bands of the validation loss (1 .. 64)")
+    p.add_argument("--val_repeats", type=int, default=1,
+                   help="passes over the validation set; pass r moves every sample on by r bands and draws other noise")
+    p.add_argument("--val_seed", type=int, default=0, help="seed of the validation plan's noise and of its forked generators")
+    p.add_argument("--val_ema", action="store_true", default=False,
+                   help="validate the EMA weights too (inside ema_scope(), keys with the suffix _ema); needs --ema_decay")
+    p.add_argument("--save_best", action="store_true", default=False,
+                   help="write best.ckpt whenever val/loss_simple (val/loss_simple_ema with --val_ema) improves")
+    p.add_argument("--loss_bands", type=int, default=0,
+                   help="break the TRAINING loss down by K timestep bands with one more small launch inside the step (this "
+                        "rank's samples only), logged as train/loss_simple/t{lo}-{hi} where the loss is logged; 0 = off")
+
+
+def check_val_args(args):
+    """The refusals of the validation flags, each with its reason, before anything is loaded."""
+    if args.val_every > 0 and not args.val_dataroot:
+        raise SystemExit("--val_every needs a validation set: give --val_dataroot (and optionally --val_latent_cache)")
+    if args.val_latent_cache and not args.val_dataroot:
+        raise SystemExit("--val_latent_cache needs --val_dataroot: the cache stores the posteriors, the prompts come from the dataset")
+    if args.val_ema and not args.ema_decay > 0.0:
+        raise SystemExit("--val_ema needs --ema_decay: without it there are no EMA weights to validate")
+    if (args.val_ema or args.save_best) and not args.val_every > 0:
+        raise SystemExit("--val_ema / --save_best need --val_every N: they act on a validation run")
+    if not 1 <= args.val_bands <= 64 or args.val_repeats < 1 or not 0 <= args.loss_bands <= 64:
+        raise SystemExit("--val_bands and --loss_bands take 1 .. 64 bands (--loss_bands 0 = off), --val_repeats >= 1")
+
+
+def build_val_dataloader(args):
+    """The validation set in order, prompt drop-out off, the last batch kept; the Trainer splits it over the ranks by index."""
+    from torch.utils.data import DataLoader
+    if args.val_latent_cache:
+        from datasets.cached_latents import CachedLatentDataset
+        dataset = CachedLatentDataset(args.val_dataroot, args.val_latent_cache, drop_rate=0.0)
+    else:
+        from datasets.custom_dataset import CustomDataset
+        dataset = CustomDataset(args.val_dataroot, drop_rate=0.0)
+    workers = min(16, os.cpu_count() or 1) if getattr(args, "num_workers", None) is None else max(0, args.num_workers)
+    return dataset, DataLoader(dataset, num_workers=workers, batch_size=args.bs, shuffle=False, drop_last=False)
 
 
 def add_lr_args(p):
@@ -150,6 +204,19 @@ def loss_model_params(min_snr_gamma: float = 0.0, loss=None, huber_delta=None) -
     return out
 
 
+def val_trainer_args(args, model) -> dict:
+    """The validation flags as Trainer arguments; nothing at the defaults."""
+    out = {}
+    if args.val_every > 0:
+        from ctrlora_amd.validation import ValPlan
+        out.update(val_check_interval=args.val_every, limit_val_batches=args.val_batches or None, val_ema=args.val_ema,
+                   save_best=args.save_best,
+                   val_plan=ValPlan(model.num_timesteps, nbands=args.val_bands, seed=args.val_seed, repeats=args.val_repeats))
+    if args.loss_bands > 0:
+        out["loss_bands"] = args.loss_bands
+    return out
+
+
 def _ema_decay(text):
     value = float(text)
     if not 0.0 <= value <= 1.0:
@@ -221,8 +288,14 @@ def main(argv=None):
     from cldm.model import create_model, load_state_dict
     from ctrlora_amd.trainer import Trainer
     args = get_parser().parse_args(argv)
+    check_val_args(args)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dataset, loader = build_dataloader(args, world, rank)
+    val_loader = None
+    if args.val_every > 0:
+        val_set, val_loader = build_val_dataloader(args)
+        if rank == 0:
+            print("Validation set size:", len(val_set))
     if rank == 0:
         print("Dataset size:", len(dataset))
         print("Number of devices:", world)
@@ -246,14 +319,24 @@ def main(argv=None):
         latent_cache.check_model(latent_cache.load_meta(args.latent_cache), model,
                                  torch.float32 if str(args.precision) in ("32", "32-true") else torch.bfloat16)
         print(f"Training from the latent cache {args.latent_cache}: the first stage encodes nothing")
+    if args.val_every > 0 and args.val_latent_cache:
+        from ctrlora_amd import latent_cache
+        import torch
+        latent_cache.check_model(latent_cache.load_meta(args.val_latent_cache), model,
+                                 torch.float32 if str(args.precision) in ("32", "32-true") else torch.bfloat16)
     gc.collect()
     name = args.name or datetime.datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
     trainer = Trainer(max_steps=args.max_steps, accumulate_grad_batches=args.gradacc, precision=args.precision,
                       callbacks=[ImageLogger(batch_frequency=args.img_logger_freq),
                                  CheckpointEveryNSteps(save_step_frequency=args.ckpt_logger_freq)],
                       default_root_dir=os.path.join("runs", name), graph_step=bool(args.graph),
-                      gradient_clip_val=args.grad_clip or None, track_grad_norm=2 if args.track_grad_norm else -1)
-    trainer.fit(model, loader)
+                      gradient_clip_val=args.grad_clip or None, track_grad_norm=2 if args.track_grad_norm else -1,
+                      **val_trainer_args(args, model))
+    trainer.fit(model, loader, val_dataloaders=val_loader)
+    if trainer.logged_val and rank == 0:
+        step, logs = trainer.logged_val[-1]
+        print(f"[trainer] val/loss_simple at step {step}: {logs['val/loss_simple']:.5f} ({len(trainer.logged_val)} runs, "
+              f"{os.path.join(trainer.log_dir, 'val_log.jsonl')})")
     if args.graph and rank == 0:
         print(f"[trainer] graph mode '{trainer.graph_mode}': {trainer.graph_replays} optimizer steps replayed, "
               f"{trainer.graph_eager_steps} launched eagerly")
